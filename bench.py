@@ -73,7 +73,13 @@ def parse():
     ap.add_argument("--gemm", choices=["h2", "x3", "f32"], default=os.environ.get("XP_GEMM_MODE", "h2"),
                     help="dense-layer back end: h2 = f32-grade split-fp16 on the f16 matrix pipe (default), x3 = f32-grade split-bf16, f32 = exact-f32 MFMA "
                          "(the reduced-precision classes x2 / bf16 are timed as extra, labelled passes only: never the headline)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (keypoints, sampled descriptors, match lists; C5: hm) as DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB; rank 0's pairs): the inputs are fixed, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(n_pairs):
@@ -316,6 +322,73 @@ def dt_hint(region_dt):
     return sorted(region_dt)[(len(region_dt) - 1) // 2]
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_DESC_BYTES = 40 << 20           # of which the descriptor samples may take at most this much
+
+
+def desc_sample_fraction(n_images, cap, dim):
+    """Share of keypoints whose descriptor rows --dump-outputs writes: fixed by the arguments (images per step, list capacity, descriptor
+    width), never by the outputs, so that two builds sample with the same fraction; 1.0 when every row fits the budget."""
+    return min(1.0, DUMP_DESC_BYTES / (n_images * cap * dim * 4))
+
+
+def desc_sample_rows(kp, frac):
+    """Rows of a keypoint list (n, 2) whose descriptors are dumped: chosen by a hash of each keypoint's coordinates, so the same keypoint is
+    sampled in every build whatever the others are (a list that differs by one keypoint still shares all other sampled rows)."""
+    import numpy as np
+    kp = np.asarray(kp, dtype=np.int64).reshape(-1, 2)
+    if frac >= 1.0:
+        return np.arange(len(kp))
+    h = (kp[:, 0].astype(np.uint64) * np.uint64(73856093)) ^ (kp[:, 1].astype(np.uint64) * np.uint64(19349663))
+    h = (h * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    return np.nonzero(h < np.uint64(int(frac * 2 ** 32)))[0]
+
+
+def dump_outputs(out_dir, res, cap, hm=None):
+    """--dump-outputs: what the timed path's last step hands its caller (PairPipeline.fetch()'s per-pair lists, and config C5's homography
+    `hm`), pairs concatenated in order, as float32 / float64 .npy files under out_dir.  counts.npy (pairs, 3) = keypoints optical, keypoints
+    thermal, matches per pair: the boundaries of the concatenated lists.  Descriptors are a sample (desc_sample_rows); desc_<spec>_rows.npy
+    holds the sampled rows' indices into that pair's keypoint list."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dim = int(res[0]["desc_optical"].shape[-1]) if res else 0
+    frac = desc_sample_fraction(2 * len(res), cap, max(dim, 1))
+    arrays = {"counts": np.array([[len(r["kp_optical"]), len(r["kp_thermal"]), len(r["match_q"])] for r in res], dtype=np.float64).reshape(-1, 3)}
+
+    def cat(key, dtype, width=None):
+        parts = [np.asarray(r[key]).astype(dtype) for r in res]
+        if width is not None:
+            parts = [p.reshape(-1, width) for p in parts]
+        return np.concatenate(parts, 0) if parts else np.zeros((0,) if width is None else (0, width), dtype)
+
+    for spec in ("optical", "thermal"):
+        arrays[f"kp_{spec}"] = cat(f"kp_{spec}", np.float32, 2)
+        rows, desc = [], []
+        for r in res:
+            sel = desc_sample_rows(r[f"kp_{spec}"], frac)
+            rows.append(sel.astype(np.float64))
+            desc.append(np.asarray(r[f"desc_{spec}"].float())[sel])
+        arrays[f"desc_{spec}_rows"] = np.concatenate(rows) if rows else np.zeros((0,))
+        arrays[f"desc_{spec}"] = np.concatenate(desc, 0).astype(np.float32) if desc else np.zeros((0, dim), np.float32)
+    arrays["match_q"] = cat("match_q", np.float64)
+    arrays["match_t"] = cat("match_t", np.float64)
+    arrays["match_d"] = cat("match_d", np.float32)
+    arrays["idx12"] = cat("idx12", np.float64)
+    arrays["idx21"] = cat("idx21", np.float64)
+    if res and "H_est" in res[0]:
+        arrays["H_est"] = np.stack([np.asarray(r["H_est"], dtype=np.float64) for r in res])
+        arrays["n_inliers"] = np.array([r["n_inliers"] for r in res], dtype=np.float64)
+        arrays["matchesMask"] = cat("matchesMask", np.float32)
+    if hm is not None:
+        arrays["hm"] = np.asarray(hm.float().cpu())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total / 2 ** 20:.1f} MB exceeds {DUMP_LIMIT_BYTES >> 20} MB: run with fewer --pairs")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
+
+
 def gpu_clock_mhz(local=0):
     """Current shader clock of THIS rank's GPU, MHz: the visible GPU's KFD node (the nodes of GPUs that are not mapped into the container are unreadable) names
     its DRM render minor -> /sys/class/drm/renderD<minor>/device/pp_dpm_sclk, the level marked '*'; rocm-smi as a fallback; None when neither answers.
@@ -532,6 +605,9 @@ def main():
         pipe.verify()
         if args.config == "c5":
             sstep.verify()                  # the head's own status word (its forward runs from its own graph): read once, after the timed region
+        if args.dump_outputs and rank == 0:
+            # the timed path's last step, before the passes below reuse the pipeline's buffers
+            dump_outputs(args.dump_outputs, pipe.fetch(), CAP, hm=(sstep.hm if args.config == "c5" else None))
         want_hygiene = args.config == "c2" and world == 1 and not args.no_other_backend and not args.graph      # (before the override below: a precision-class
         if args.config != "c2" or world > 1 or args.precision_class != "f32":                                     #  run keeps the rotating-input / sustained regions)
             args.no_other_backend = True        # the extra passes (other back ends, precision classes, PCIe-inclusive) are single-GPU records: an N-rank run stays short

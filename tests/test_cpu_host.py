@@ -289,3 +289,46 @@ def test_bench_pmc_numbers_are_tied_to_the_kernel_sources(tmp_path):
     assert [os.path.basename(x) for x in bench.pmc_files("c2", "amp16f")] == ["pmc_traffic_amp16f.json", "pmc_mfma_amp16f.json"]
     # static reference data is labelled as such
     assert bench.dense_engine_ceilings().get("static_reference_data") is True
+
+
+def test_bench_dump_outputs_layout_budget_and_stable_sample(tmp_path):
+    """bench.py --dump-outputs: the last step's caller-visible lists as float32 / float64 .npy under the 64 MB budget, descriptors sampled by
+    keypoint coordinates (a keypoint missing from one list leaves every other sampled row in place), identical files for identical results."""
+    import importlib, sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(0)
+    B, cap, D, n = 8, 8192, 256, 4100          # the C2 step: 16 lists of ~4k keypoints would be 67 MB of descriptors in full
+
+    def pair(i):
+        kp = np.stack(np.unravel_index(rng.choice(480 * 640, n, replace=False), (480, 640)), 1)
+        m = 1500 + i
+        return dict(kp_optical=torch.from_numpy(kp).long(), kp_thermal=torch.from_numpy(kp[::-1].copy()).long(),
+                    desc_optical=torch.from_numpy(rng.standard_normal((n, D)).astype(np.float32)),
+                    desc_thermal=torch.from_numpy(rng.standard_normal((n, D)).astype(np.float32)),
+                    match_q=np.arange(m, dtype=np.int32), match_t=np.arange(m, dtype=np.int32)[::-1].copy(), match_d=rng.random(m).astype(np.float32),
+                    idx12=np.arange(n, dtype=np.int32), idx21=np.arange(n, dtype=np.int32))
+    res = [pair(i) for i in range(B)]
+    a = bench.dump_outputs(str(tmp_path / "a"), res, cap)
+    bench.dump_outputs(str(tmp_path / "b"), res, cap, hm=torch.ones(B, 8))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in a) and "hm.npy" in os.listdir(tmp_path / "b")
+    total = 0
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64 << 20
+    assert a["counts"].tolist() == [[n, n, 1500 + i] for i in range(B)]
+    assert len(a["kp_optical"]) == B * n and len(a["match_q"]) == sum(1500 + i for i in range(B))
+    frac = bench.desc_sample_fraction(2 * B, cap, D)
+    sel0 = bench.desc_sample_rows(res[0]["kp_optical"], frac)
+    assert 0 < len(sel0) < n and np.array_equal(a["desc_optical_rows"][:len(sel0)], sel0)
+    assert np.array_equal(a["desc_optical"][:len(sel0)], res[0]["desc_optical"].numpy()[sel0])
+    # drop one keypoint: the other sampled keypoints are still sampled
+    kp = res[0]["kp_optical"].numpy()
+    keep = set(map(tuple, kp[sel0]))
+    sel1 = bench.desc_sample_rows(kp[1:], frac)
+    assert set(map(tuple, kp[1:][sel1])) == keep - {tuple(kp[0])}

@@ -116,6 +116,33 @@ def test_bench_hygiene_keys_and_fast_class_label():
     assert 0 < roof["frac"] < 1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the timed path's last step (C2 at 8 pairs) as float .npy files within 64 MB: the lists agree with the line's own
+    keypoint / match means, the descriptor sample is the coordinate-keyed one, and ms_per_step is the reported region over its K steps."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    d = tmp_path / "dump"
+    r = _run(1, ("--no-cpu-baseline", "--no-h2d", "--dump-outputs", str(d)))
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 2 and abs(out["ms_per_step"] * 2 * out["value"] / 1e3 - 16) < 0.01 * 16
+    a = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    counts = a["counts"]
+    assert counts.shape == (8, 3)
+    assert abs(counts[:, :2].mean() - out["config"]["keypoints_per_image_mean"]) < 0.1 and abs(counts[:, 2].mean() - out["config"]["matches_per_pair_mean"]) < 0.1
+    frac = bench.desc_sample_fraction(16, bench.CONFIGS["c2"]["cap"], 256)
+    for spec, c in (("optical", 0), ("thermal", 1)):
+        kp = a[f"kp_{spec}"]
+        assert len(kp) == counts[:, c].sum() and kp.shape[1] == 2
+        first = kp[:int(counts[0, c])]
+        sel = bench.desc_sample_rows(first, frac)
+        assert np.array_equal(a[f"desc_{spec}_rows"][:len(sel)], sel) and a[f"desc_{spec}"].shape == (len(a[f"desc_{spec}_rows"]), 256)
+        assert np.isfinite(a[f"desc_{spec}"]).all()
+    assert len(a["match_q"]) == len(a["match_t"]) == len(a["match_d"]) == counts[:, 2].sum()
+
+
 def test_bench_launcher_refuses_more_gpus_than_visible():
     n = torch.cuda.device_count() + 1
     r = _run(n)

@@ -20,8 +20,10 @@ def source_hash(csrc: str = CSRC, include: str = os.path.join(HERE, "..", "inclu
     quoted in a bench line that were collected on OTHER kernel sources are flagged `traffic_stale` / `frac_mfma_busy_pmc_stale`."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.h")) +
-                   glob.glob(os.path.join(include, "*.h")))
+    # include/ first, then csrc/, each by name: the order must not depend on where the two directories live
+    files = (sorted(glob.glob(os.path.join(include, "*.h")), key=os.path.basename) +
+             sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.h")),
+                    key=os.path.basename))
     for f in files:
         if os.path.basename(f) == "xp_knobs.h":      # the registry of knob DESCRIPTIONS: text, not kernel code
             continue
