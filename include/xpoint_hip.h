@@ -481,6 +481,37 @@ int xp_warp_perspective(const void* src, void* dst, const double* M, int batch, 
                         int dst_channels, int dtype, int inverse_map, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Homographic adaptation (reference homographies.py:40-300; xpoint_amd/homographies.py drives these per chunk of homographies;
+ * arithmetic spec in csrc/homadapt.hip and DESIGN.md "Homographic adaptation").  All pointers are device pointers, f32 unless noted.
+ *   xp_ha_warp: kornia 0.1.4 warp_perspective_tensor semantics (torch.linspace grid, plain projective division, grid_sample with
+ *     align_corners = False).  src (n_src, Hs, Ws) -> dst (n_dst, Hd, Wd); dst image i samples src image i % n_src with the normalised
+ *     3 x 3 matrix M[i / n_src] (row-major, the matrix kornia passes to homography_warp).  mode XP_HA_NEAREST / XP_HA_BILINEAR,
+ *     padding XP_HA_ZEROS / XP_HA_REFLECTION.
+ *   xp_ha_valid_mask: compute_valid_mask for K homographies Hm (K, 9) f64 (forward maps): OpenCV's INTER_NEAREST warp of ones, then the
+ *     (2r+1)^2 erosion, with a zero 1-pixel frame when mask_border != 0.  mask (K, H, W) u8 in {0, 1}; tmp: K * H * W bytes (unused
+ *     when erosion_radius == 0).
+ *   xp_ha_gaussian: depthwise ksize x ksize filter (weights row-major) behind a reflection pad of ksize / 2, (n, H, W) -> (n, H, W).
+ *   xp_ha_accumulate: the fused unwarp / aggregate / accumulate over the n_views views of one chunk.  prob (n_views, S, B, H, W) with
+ *     S = 1 (XP_HA_SINGLE) or 2 (optical, thermal); M (n_views - first_direct, 9) the normalised matrices of inverse(H); mask
+ *     (n_views - first_direct, H, W) u8 from xp_ha_valid_mask; acc0 / acc1 (window only) / count (B, H, W) the running sums.
+ *     first_direct: view 0 is the original images (sums initialised, count = 1).  finalize: divide by count, sqrt (prod) or
+ *     * 0.5 (sum), zero where count < min_count (min_count > 0). */
+#define XP_HA_NEAREST 0
+#define XP_HA_BILINEAR 1
+#define XP_HA_ZEROS 0
+#define XP_HA_REFLECTION 1
+#define XP_HA_SINGLE 0
+#define XP_HA_PROD 1
+#define XP_HA_SUM 2
+#define XP_HA_WINDOW 3
+int xp_ha_warp(const float* src, float* dst, const float* M, int n_src, int n_dst, int Hs, int Ws, int Hd, int Wd, int mode, int padding,
+               void* stream);
+int xp_ha_valid_mask(const double* Hm, uint8_t* mask, uint8_t* tmp, int K, int H, int W, int erosion_radius, int mask_border, void* stream);
+int xp_ha_gaussian(const float* src, float* dst, const float* weights, int n, int H, int W, int ksize, void* stream);
+int xp_ha_accumulate(const float* prob, const float* M, const uint8_t* mask, float* acc0, float* acc1, float* count, int B, int n_views,
+                     int first_direct, int H, int W, int mode, int window_size, int weighted, int finalize, float min_count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

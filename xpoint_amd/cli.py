@@ -3,12 +3,21 @@
 
     python -m xpoint_amd.cli align     -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e] [-o out.npz]
     python -m xpoint_amd.cli keypoints -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-o out.npz]
+    python -m xpoint_amd.cli export    -y configs/config_export_keypoints.yaml -m model_weights/XPoint-EXP1 -v latest -o labels.npz
+                                       [-i 0] [-n all] [-s 0] [--chunk K]
 
 What is kept from the scripts: the YAML handling (model params from <model-dir>/params.yaml overwrite config['model'], the
 `use_attention` height / width patch of predict_align_image_pair.py:50-54), `<model-dir>/<version>.model` loaded with
 `strict=False` after `fix_model_weigth_keys`, the seeds, the per-sample flow.  What is not: plotting (-p, -r) and the HDF5
 datasets — the dataset must be a folder dataset (`dataset.foldername`, xpoint_amd/datasets.py).  `-e` adds the registration
-step (robust homography per pair) and prints the inlier counts.  Prints one line per sample and a timing summary."""
+step (robust homography per pair) and prints the inlier counts.  Prints one line per sample and a timing summary.
+
+`export` is export_keypoints.py: label export by homographic adaptation (xpoint_amd.homographies, config key
+prediction.homographic_adaptation) with the model params of <model-dir>/params.yaml, takes_pair and the homography head off, seeds as
+in the script, box_nms with prediction.nms / detection_threshold / topk, keypoints = nonzero(prob > detection_threshold).  The output
+is an .npz with the keys <name>/keypoints, or <name>/keypoints_optical and <name>/keypoints_thermal for the window aggregation.  Not
+supported: HDF5 output, the HDF5 datasets, -skip and the -f backup files (h5py is not available); the dataset must be a folder dataset.
+--chunk sets the homographies per forward (default: the library's); it does not change the result."""
 from __future__ import annotations
 
 import argparse
@@ -57,18 +66,23 @@ def build(config: dict, model_dir: str, version: str, device: str):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m xpoint_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('flow', choices=['align', 'keypoints'])
+    ap.add_argument('flow', choices=['align', 'keypoints', 'export'])
     ap.add_argument('-y', '--yaml-config', default='configs/cipdp.yaml', help='YAML config file')
     ap.add_argument('-m', '--model-dir', default='model_weights/xpoint', help='Directory of the model')
     ap.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
     ap.add_argument('-i', '--index', default=0, type=int, help='Index of the first sample')
-    ap.add_argument('-n', '--count', default=1, type=int, help='Number of consecutive samples')
+    ap.add_argument('-n', '--count', default=None, type=int, help='Number of consecutive samples (default 1; export: all)')
     ap.add_argument('-e', dest='evaluation', action='store_true', help='align: also estimate the homography of every pair and warp the optical image with it')
     ap.add_argument('--save-warped', default=None, metavar='DIR', help='align -e: write the warped optical image of every sample to DIR/<name>_warped.png')
     ap.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
     ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz')
+    ap.add_argument('--chunk', default=None, type=int, help='export: homographies per forward (does not change the result)')
     ap.add_argument('--device', default='cuda:0')
     args = ap.parse_args(argv)
+    if args.flow == 'export':
+        return export(args)
+    if args.count is None:
+        args.count = 1
 
     random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
     config = load_config(args.yaml_config, args.model_dir)
@@ -114,6 +128,59 @@ def main(argv=None):
     print(f"{args.flow}: {sum(1 for k in out if k.endswith('/kp_optical'))} sample(s), {t_total * 1e3:.1f} ms")
     if args.output:
         np.savez(args.output, **out)
+    return out
+
+
+def export(args):
+    """export_keypoints.py (see the module docstring)."""
+    if not args.output:
+        raise SystemExit("export: -o/--output (.npz) is required")
+    with open(args.yaml_config, 'r') as f:
+        config = yaml.load(f, Loader=yaml.FullLoader)
+    with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
+        config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']          # overwrite the model params
+    ds = config.get('dataset', {})
+    if ds.get('filename') is not None or ds.get('foldername') is None:
+        raise SystemExit("export: only folder datasets are supported (dataset.foldername); HDF5 datasets (dataset.filename) need h5py, "
+                         "which is not available")
+    config['model']['takes_pair'] = False                                         # export_keypoints.py
+    if 'homography_regression_head' in config['model']:
+        config['model']['homography_regression_head']['check'] = False
+        if 'disable_hmhead' in config['prediction']:
+            config['model']['homography_regression_head']['check'] = not bool(config['prediction']['disable_hmhead'])
+    torch.manual_seed(args.seed); random.seed(args.seed); np.random.seed(args.seed)
+    if not torch.cuda.is_available():
+        raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
+    from . import utils
+    dataset, net = build(config, args.model_dir, args.version, args.device)
+    pred = config['prediction']
+    ha_cfg = pred['homographic_adaptation']
+    window = ha_cfg.get('aggregation', 'prod') == 'window'
+    bs = int(pred.get('batchsize', 1))
+    last = len(dataset) if args.count is None else min(args.index + args.count, len(dataset))
+    out = {}
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        for i0 in range(args.index, last, bs):
+            batch = dataset.load_batch(list(range(i0, min(i0 + bs, last))), args.device)
+            r = utils.homographic_adaptation_multispectral(batch, net, ha_cfg, chunk=args.chunk)
+            probs = {'optical': r['out_optical']['prob'], 'thermal': r['out_thermal']['prob']} if window else {'': r['out']['prob']}
+            if pred['nms'] > 0:
+                probs = {k: utils.box_nms(v, pred['nms'], pred['detection_threshold'], keep_top_k=pred['topk'], on_cpu=pred.get('cpu_nms', False))
+                         for k, v in probs.items()}
+            for b, name in enumerate(batch['name']):
+                counts = []
+                for k, v in probs.items():
+                    kp = torch.nonzero(v[b].squeeze() > pred['detection_threshold']).cpu().numpy()
+                    out[f"{name}/keypoints" + (f"_{k}" if k else "")] = kp
+                    counts.append(len(kp))
+                print(f"{name}: {' / '.join(map(str, counts))} keypoints")
+    torch.cuda.synchronize()
+    print(f"export: {len(out) // len(probs) if out else 0} sample(s), {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    d = os.path.dirname(args.output)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    np.savez(args.output, **out)
     return out
 
 

@@ -568,7 +568,8 @@ __global__ __launch_bounds__(NW * 64, H2 ? 2 : ((C <= 96 ? 8 : 4) / NW)) void ml
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rl = (r & 3) + 8 * (r >> 2) + 4 * g;
-                const float* rp = xb + ((INTERIOR || m0 + rl < p.M) ? rl : 0) * C + col;
+                // a row past M reads row M - 1 (never stored): a whole wave can lie past M in the last workgroup, so row m0 is not safe
+                const float* rp = (INTERIOR || m0 + rl < p.M) ? xb + rl * C + col : p.X + (int64_t)(p.M - 1) * C + col;
                 rv[r] = PRE ? __hip_atomic_load(rp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *rp;
             }
 #pragma unroll

@@ -31,25 +31,6 @@ struct WarpParams {
     int Hs, Ws, Hd, Wd, C, Cd, inverse_map;
 };
 
-__device__ __forceinline__ void warp_invert3(const double* __restrict__ S, double (&t)[9]) {
-    // OpenCV cv::invert, 3 x 3 double, DECOMP_LU: det3 and the cofactors in this operand order
-    double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-    if (d != 0.0) {
-        d = 1.0 / d;
-        t[0] = (S[4] * S[8] - S[5] * S[7]) * d;
-        t[1] = (S[2] * S[7] - S[1] * S[8]) * d;
-        t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-        t[3] = (S[5] * S[6] - S[3] * S[8]) * d;
-        t[4] = (S[0] * S[8] - S[2] * S[6]) * d;
-        t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-        t[6] = (S[3] * S[7] - S[4] * S[6]) * d;
-        t[7] = (S[1] * S[6] - S[0] * S[7]) * d;
-        t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
-    } else {
-        for (int k = 0; k < 9; ++k) t[k] = 0.0;
-    }
-}
-
 __device__ __forceinline__ int warp_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 // source element (channel c) at (sx, sy), 0 outside.  MODE 0: u8 source; 1: f32 source; 2: f32 source quantised on load as the reference
@@ -76,7 +57,7 @@ __global__ __launch_bounds__(256) void warp_perspective_kernel(WarpParams p) {
     if (threadIdx.x == 0) {
         const double* S = p.M + (size_t)b * 9;
         double t[9];
-        if (p.inverse_map) { for (int k = 0; k < 9; ++k) t[k] = S[k]; } else warp_invert3(S, t);
+        if (p.inverse_map) { for (int k = 0; k < 9; ++k) t[k] = S[k]; } else xp_cv_invert3(S, t);
         for (int k = 0; k < 9; ++k) s_m[k] = t[k];
     }
     __syncthreads();

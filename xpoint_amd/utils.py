@@ -370,3 +370,8 @@ def checkerboard_visualization(img_visible, img_other, H, cell_size=50):
     y = torch.arange(Ho, device=img_other.device)[:, None] // int(cell_size)
     x = torch.arange(Wo, device=img_other.device)[None, :] // int(cell_size)
     return torch.where(((x + y) % 2).bool(), warped, img_other)
+
+
+# ---------------------------------------------------------------- homographic adaptation (homographies.py), exported like xpoint.utils does
+from .homographies import (homography_adaptation_default_config, sample_homography, homographic_adaptation,  # noqa: E402,F401
+                           homographic_adaptation_multispectral)
