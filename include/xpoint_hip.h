@@ -479,6 +479,11 @@ int xp_find_homography(const float* src, const float* dst, const int* counts, in
 #define XP_WARP_F32_AS_U8 2
 int xp_warp_perspective(const void* src, void* dst, const double* M, int batch, int Hs, int Ws, int Hd, int Wd, int channels,
                         int dst_channels, int dtype, int inverse_map, void* stream);
+/* The same with a valid mask (batch, Hs, Ws) u8, nonzero = valid, for XP_WARP_F32_AS_U8 only: the source is multiplied by the mask before
+ * it is quantised, as the reference's `optical *= mask_optical` (predict_align_image_pair.py:267) — an invalid pixel reads 0.  mask == NULL
+ * is xp_warp_perspective. */
+int xp_warp_perspective_masked(const void* src, const uint8_t* mask, void* dst, const double* M, int batch, int Hs, int Ws, int Hd, int Wd,
+                               int channels, int dst_channels, int dtype, int inverse_map, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Homographic adaptation (reference homographies.py:40-300; xpoint_amd/homographies.py drives these per chunk of homographies;

@@ -174,6 +174,85 @@ def _ref_pair_flow(net, ref_utils, i, H, W, thr=0.015, nms=8, topk=0):
             np.array([m.distance for m in ms], dtype=np.float32))
 
 
+def savez_deterministic(path, arrays):
+    """np.savez_compressed with fixed zip member timestamps and order, so that a generator run reproduces its file byte for byte."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[name]), allow_pickle=False)
+
+
+def _g25_case(g, tag, net, ref_utils, H, W, n_pairs, n_punch, store_prob, thr=0.015, nms=8):
+    """Pairs 0..n_pairs-1 of the synthetic inputs through the REAL reference with the non-trivial masks of synth.g25_masks (pairs 0..2) and,
+    for pair 3, ones minus 5x5 squares centred on the n_punch strongest keypoints of the reference's UNMASKED NMS output.  Both flows:
+    predict_align_image_pair.py:195-243 (prob * mask -> box_nms -> nonzero) and predict_keypoints.py:205-215 (box_nms on the unmasked prob ->
+    nonzero((p > thr) * mask)); NNMatcher on the first; the SHA-256 of the masked, quantised im_optical of predict_align_image_pair.py:267-271."""
+    import hashlib
+    for i in range(n_pairs):
+        base = synth.make_pair_batch(i, 1, H, W)
+        with torch.no_grad():
+            o, t, _ = net(synth.to_torch(base))             # the valid masks do not enter the forward
+        outs = {"optical": o, "thermal": t}
+        unmasked_nms = {s: ref_utils.box_nms(outs[s]["prob"], nms, thr, keep_top_k=0, on_cpu=True) for s in outs}
+        if i < 3:
+            masks = dict(zip(("optical", "thermal"), synth.g25_masks(i, H, W)))
+        else:
+            masks = {}
+            for spec in ("optical", "thermal"):
+                raw = outs[spec]["prob"][0, 0].numpy()
+                kp = torch.nonzero(unmasked_nms[spec][0].squeeze() > thr).numpy()
+                sc = raw[kp[:, 0], kp[:, 1]]
+                top = kp[np.lexsort((kp[:, 1], kp[:, 0], -sc))[:n_punch]]        # strongest first; ties by (y, x)
+                g[f"{tag}p{i}/centres_{spec}"] = top.astype(np.int16)
+                masks[spec] = synth.mask_punched(H, W, top, 2)
+        descs = []
+        for spec in ("optical", "thermal"):
+            r, m = outs[spec], torch.from_numpy(masks[spec][None, None])
+            raw = r["prob"][0, 0]
+            g[f"{tag}p{i}/mask_{spec}"] = np.packbits(masks[spec].ravel())
+            masked = r["prob"] * m
+            pn = ref_utils.box_nms(masked, nms, thr, keep_top_k=0, on_cpu=True)
+            kp = torch.nonzero((pn[0].squeeze() > thr).float())
+            descs.append(ref_utils.interpolate_descriptors(kp, r["desc"][0], H, W))
+            g[f"{tag}p{i}/kp_{spec}"] = kp.numpy().astype(np.int16)
+            g[f"{tag}p{i}/score_{spec}"] = raw[kp[:, 0], kp[:, 1]].numpy()
+            kpk = torch.nonzero((unmasked_nms[spec][0].squeeze() > thr).float() * m[0, 0])
+            g[f"{tag}p{i}/kpk_{spec}"] = kpk.numpy().astype(np.int16)
+            if store_prob:
+                g[f"{tag}p{i}/prob_{spec}"] = raw.numpy()
+                g[f"{tag}p{i}/prob_masked_{spec}"] = masked[0, 0].numpy()
+        ms = ref_utils.get_matches(descs[0].numpy(), descs[1].numpy(), "nnmatcher", False, threshold=10.0)
+        g[f"{tag}p{i}/matches"] = np.array([[m.queryIdx, m.trainIdx] for m in ms], dtype=np.int16).reshape(-1, 2)
+        g[f"{tag}p{i}/match_dist"] = np.array([m.distance for m in ms], dtype=np.float32)
+        optical = torch.from_numpy(base["optical"]["image"]).squeeze().clone()
+        optical *= torch.from_numpy(masks["optical"])                                   # predict_align_image_pair.py:267
+        im = (np.clip(optical.numpy(), 0.0, 1.0) * 255.0).astype(np.uint8)             # :270, before GRAY2RGB
+        g[f"{tag}p{i}/im_optical_sha256"] = np.frombuffer(hashlib.sha256(im.tobytes()).digest(), dtype=np.uint8).copy()
+        print("g25", tag or "480x640", "pair", i, "kpts", len(g[f"{tag}p{i}/kp_optical"]), len(g[f"{tag}p{i}/kp_thermal"]), "predict_keypoints",
+              len(g[f"{tag}p{i}/kpk_optical"]), len(g[f"{tag}p{i}/kpk_thermal"]), "matches", len(ms), flush=True)
+
+
+def gen_g25():
+    """G25 — non-trivial valid masks end to end through the REAL reference: 4 pairs of 480x640 (full XPoint-EXP1 config, the images of
+    g15's pairs 0..3), each with masks built to hit a masking edge (synth.g25_masks; pair 3 punches the 64 strongest unmasked detections),
+    plus a reduced 64x96 model (EMBED_DIM 32, prefix "s/") whose raw and masked prob maps are stored for the CPU oracle.  Masks as
+    np.packbits of the (H, W) bool mask; keypoints (y, x) int16 of both flows (kp_* = predict_align_image_pair, kpk_* = predict_keypoints),
+    the reference's score at each kp_*, NNMatcher pairs / distances, and the SHA-256 of the masked uint8 im_optical."""
+    torch.set_num_threads(1)
+    stubs.install()
+    import xpoint.utils as ref_utils
+    H, W = 480, 640
+    g = {"meta": np.array([4, H, W], dtype=np.int32), "s/meta": np.array([4, 64, 96], dtype=np.int32)}
+    cfg = synth.xpoint_exp1_config(64, 96, vssm={"EMBED_DIM": 32})
+    _g25_case(g, "s/", build_ref.build_reference_xpoint(cfg, synth.make_state_dict(cfg)), ref_utils, 64, 96, 4, 8, True)
+    cfg = synth.xpoint_exp1_config(H, W)
+    _g25_case(g, "", build_ref.build_reference_xpoint(cfg, synth.make_state_dict(cfg)), ref_utils, H, W, 4, 64, False)
+    savez_deterministic(os.path.join(OUT, "g25_masked_pairs.npz"), g)
+
+
 def gen_g18_part(first, last, out_path):
     """One shard of G18 (pairs first..last-1 of BASELINE config C3's 64-pair batch) through the REAL reference; run several shards as
     separate single-thread processes, then `g18merge`."""

@@ -240,3 +240,73 @@ def test_g23_threshold_matcher_and_knn_restatements(golden):
     np.testing.assert_allclose(dist, np.sqrt(np.take_along_axis(dm, order, 1)), rtol=1e-12)
     with pytest.raises(ValueError):
         xo.knn_ratio_matches(d1, d2[:1])
+
+
+def _unpack_mask(packed, H, W):
+    return np.unpackbits(packed, count=H * W).reshape(H, W).astype(bool)
+
+
+def test_g25_masked_flows_64x96(golden):
+    """The oracle's masked flows against the REAL reference on the reduced model (g25 "s/"): predict_align_image_pair's
+    prob * mask -> box_nms -> nonzero, and predict_keypoints' box_nms on the UNMASKED prob -> nonzero((p > thr) * mask), on the
+    reference's own prob maps and masks (quad / uneven frame, frame + hole + islands, all zeros, punched peaks).  Exact lists."""
+    g = golden("g25_masked_pairs.npz")
+    n, H, W = [int(v) for v in g["s/meta"]]
+    for i in range(n):
+        for spec in ("optical", "thermal"):
+            pre = f"s/p{i}/"
+            m = torch.from_numpy(_unpack_mask(g[pre + f"mask_{spec}"], H, W))
+            prob = torch.from_numpy(g[pre + f"prob_{spec}"])
+            masked = prob * m
+            assert torch.equal(masked, torch.from_numpy(g[pre + f"prob_masked_{spec}"]))
+            nms = xo.box_nms(masked[None, None], 8, 0.015)
+            kp = xo.extract_keypoints(nms[0, 0], 0.015)
+            assert np.array_equal(kp.numpy(), g[pre + f"kp_{spec}"]), (i, spec)
+            assert np.array_equal(prob.numpy()[kp[:, 0], kp[:, 1]], g[pre + f"score_{spec}"])
+            kpk = xo.extract_keypoints(xo.box_nms(prob[None, None], 8, 0.015)[0, 0], 0.015, m)
+            assert np.array_equal(kpk.numpy(), g[pre + f"kpk_{spec}"]), (i, spec)
+            assert bool(m[kp[:, 0], kp[:, 1]].all()) and bool(m[kpk[:, 0], kpk[:, 1]].all())
+        if i == 2:
+            assert len(g[pre + "kp_optical"]) == 0 and len(g[pre + "kpk_optical"]) == 0 and len(g[pre + "matches"]) == 0
+    # pair 3: masking before NMS releases detections the punched peaks suppressed, which masking after NMS keeps suppressed
+    for spec in ("optical", "thermal"):
+        a = {tuple(p) for p in g[f"s/p3/kp_{spec}"].tolist()}
+        b = {tuple(p) for p in g[f"s/p3/kpk_{spec}"].tolist()}
+        assert a - b, spec
+
+
+def test_g25_mask_builders_reproduce_fixture(golden):
+    """synth's integer mask builders reproduce the packed masks stored in g25 (pairs 0..2, both sizes); pair 3's are the punched
+    construction around the stored centres."""
+    g = golden("g25_masked_pairs.npz")
+    for pre, meta in (("", "meta"), ("s/", "s/meta")):
+        n, H, W = [int(v) for v in g[meta]]
+        for i in range(3):
+            mo, mt = synth.g25_masks(i, H, W)
+            assert np.array_equal(g[f"{pre}p{i}/mask_optical"], np.packbits(mo.ravel())), (pre, i)
+            assert np.array_equal(g[f"{pre}p{i}/mask_thermal"], np.packbits(mt.ravel())), (pre, i)
+        for spec in ("optical", "thermal"):
+            m = synth.mask_punched(H, W, g[f"{pre}p3/centres_{spec}"], 2)
+            assert np.array_equal(g[f"{pre}p3/mask_{spec}"], np.packbits(m.ravel())), (pre, spec)
+    H, W = 480, 640
+    f = synth.mask_frame(H, W, 3, 5, 7, 9)
+    assert f.sum() == (H - 10) * (W - 14) and f[3, 9] and not f[2, 9] and not f[3, 8] and f[H - 8, W - 6] and not f[H - 7, W - 6]
+    q = synth.mask_quad(H, W)
+    assert q[H // 2, W // 2] and not q[0, 0] and not q[H - 1, W - 1] and 0.5 < q.mean() < 0.95
+    isl = synth.mask_frame_hole_islands(H, W)
+    lone = isl & ~np.pad(isl, 1)[:-2, 1:-1] & ~np.pad(isl, 1)[2:, 1:-1] & ~np.pad(isl, 1)[1:-1, :-2] & ~np.pad(isl, 1)[1:-1, 2:]
+    assert lone.sum() >= 9                                       # the isolated single valid pixels
+    im = (np.clip(synth.make_image(0, "optical", H, W)[0] * synth.g25_masks(0, H, W)[0], 0, 1) * 255.0).astype(np.uint8)
+    import hashlib
+    assert hashlib.sha256(im.tobytes()).digest() == g["p0/im_optical_sha256"].tobytes()
+
+
+def test_make_pair_batch_masks_stay_all_ones():
+    """Every fixture except g25 was built from make_pair_batch's all-ones masks: they must stay so."""
+    d = synth.make_pair_batch(3, 2, 16, 24)
+    for spec in ("optical", "thermal"):
+        m = d[spec]["valid_mask"]
+        assert m.dtype == bool and m.shape == (2, 1, 16, 24) and m.all()
+    d2 = synth.with_masks(d, np.zeros((2, 16, 24), bool), np.ones((2, 16, 24), bool))
+    assert d["optical"]["valid_mask"].all() and not d2["optical"]["valid_mask"].any()
+    assert d2["optical"]["valid_mask"].shape == (2, 1, 16, 24) and d2["optical"]["image"] is d["optical"]["image"]

@@ -103,6 +103,7 @@ _SIGNATURES = {
     "xp_gather_match_points": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "xp_find_homography": [c_p, c_p, c_p, c_i, c_i, c_f, c_i, ctypes.c_uint, c_p, c_p, c_p, c_p, c_sz, c_p],
     "xp_warp_perspective": [c_p, c_p, c_p] + [c_i] * 9 + [c_p],
+    "xp_warp_perspective_masked": [c_p, c_p, c_p, c_p] + [c_i] * 9 + [c_p],
     "xp_ha_warp": [c_p] * 3 + [c_i] * 8 + [c_p],
     "xp_ha_valid_mask": [c_p] * 3 + [c_i] * 5 + [c_p],
     "xp_ha_gaussian": [c_p] * 3 + [c_i] * 4 + [c_p],

@@ -664,8 +664,9 @@ extern "C" int xp_stage_pair_batch(const float* optical, const float* thermal, f
 }
 
 extern "C" int xp_mul_mask(const float* x, const uint8_t* mask, float* y, int64_t n, void* stream) {
+    XP_CHECK_ARG(n >= 0, "xp_mul_mask: negative size");
+    if (n == 0) return XP_OK;                   // (an empty torch tensor has a null data pointer)
     XP_CHECK_ARG(x && mask && y, "xp_mul_mask: null pointer");
-    if (n == 0) return XP_OK;
     XpProfScope prof("mul_mask", (hipStream_t)stream, 1.0 * n, 9.0 * n);
     if (n % 4 == 0 && ((((uintptr_t)x | (uintptr_t)y) & 15) == 0) && (((uintptr_t)mask & 3) == 0))
         hipLaunchKernelGGL(mul_mask4_kernel, dim3(xp_cdiv(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x),

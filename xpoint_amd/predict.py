@@ -35,8 +35,8 @@ def predict_align_image_pair(net, data, cfg_prediction=None, match_mode="strict_
     desc_optical, desc_thermal (N,D), matches [DMatch]).  estimate_homography=True adds the registration step of
     predict_align_image_pair.py:287-303: H_est (3,3) float64 mapping optical (x, y) to thermal (identity when fewer than
     4 matches, as the reference) and matchesMask, from `utils.find_homography` at `reprojection_threshold` (default 3), and — unless
-    warp_optical=False — the script's final product (predict_align_image_pair.py:271, 308): `warped_optical`, the optical image quantised
-    to uint8 RGB as the reference builds `im_optical` and warped by H_est into the thermal frame (`utils.warp_perspective`: INTER_LINEAR,
+    warp_optical=False — the script's final product (predict_align_image_pair.py:267-271, 308): `warped_optical`, the optical image multiplied
+    by its valid mask and quantised to uint8 RGB as the reference builds `im_optical`, and warped by H_est into the thermal frame (`utils.warp_perspective`: INTER_LINEAR,
     BORDER_CONSTANT; (H, W, 3) uint8 on the device).  warp_optical=True without estimate_homography is an error."""
     if warp_optical and not estimate_homography:
         raise ValueError("predict_align_image_pair: warp_optical needs estimate_homography=True (the warp uses H_est)")
@@ -72,7 +72,9 @@ def predict_align_image_pair(net, data, cfg_prediction=None, match_mode="strict_
             r["H_est"] = H_est if H_est is not None else np.eye(3)
             r["matchesMask"] = mask.ravel().tolist() if mask is not None else []
             if warp_optical:
-                r["warped_optical"] = utils.warp_perspective(data['optical']['image'][i, 0], r["H_est"], quantise_u8=True, dst_channels=3)
+                # the reference masks the optical image before quantising it (predict_align_image_pair.py:267-271); data is left unchanged
+                r["warped_optical"] = utils.warp_perspective(data['optical']['image'][i, 0], r["H_est"], quantise_u8=True, dst_channels=3,
+                                                             mask=data['optical']['valid_mask'][i])
         results.append(r)
     return out_o, out_t, results
 
@@ -330,8 +332,11 @@ class PairPipeline:
                                               float(self.pred.get('reprojection_threshold', 3.0)), self.ransac_iters, 0, ptr(h["H"]), ptr(h["mask"]),
                                               ptr(h["n_inliers"]), ptr(h["ws"]), h["ws"].numel() * 8, st), "xp_find_homography")
             if self.warp_optical:
-                _lib.check(lib.xp_warp_perspective(ptr(self.images_b[k]), ctypes.c_void_p(h["warped"].data_ptr()), ctypes.c_void_p(h["H"].data_ptr()),
-                                                   B, H, W, H, W, 1, 1, 2, 0, st), "xp_warp_perspective")
+                # masked steps: the optical image times its mask, quantised (predict_align_image_pair.py:267-271) — by the warp's load, so the staged
+                # images stay unmasked (a range-guard repair re-encodes the latest step from them, _settle_engine)
+                _lib.check(lib.xp_warp_perspective_masked(ptr(self.images_b[k]), ctypes.c_void_p(self.mask_b[k].data_ptr()) if masked else None,
+                                                          ctypes.c_void_p(h["warped"].data_ptr()), ctypes.c_void_p(h["H"].data_ptr()),
+                                                          B, H, W, H, W, 1, 1, 2, 0, st), "xp_warp_perspective_masked")
         return self
 
     def match_stats(self):
@@ -359,7 +364,11 @@ class PairPipeline:
         host memory, at every replay).
         One stream: one graph of encoder + detection + matching.  Overlapped pipeline: per output buffer (two of them), one
         graph per encoder image group and one for the detection / matching kernels, each replayed on its own stream and
-        chained by the same events as the eager schedule — the cross-step overlap survives capture."""
+        chained by the same events as the eager schedule — the cross-step overlap survives capture.
+        Masks: the graphs are captured with or without the masking kernel, as the capture call is; every replay must match that
+        (both masks when captured with masks — new ones at every replay are fine — neither when captured without) and raises
+        ValueError otherwise, instead of ignoring the masks or applying those staged by an earlier step.  Capture a second pipeline
+        for the other case."""
         with torch.cuda.device(self.device):
             for _ in range(self.depth):                         # warm-up outside capture: one-time allocations, every buffer set
                 self._run(optical, thermal, mask_optical, mask_thermal)
@@ -369,6 +378,7 @@ class PairPipeline:
             self._capture_graphs()
             if not self.overlap:
                 def replay(optical, thermal, mask_optical=None, mask_thermal=None):
+                    self._check_replay_masks(mask_optical, mask_thermal)
                     self._stage_inputs(0, optical, thermal, mask_optical, mask_thermal)
                     self._last = (0, mask_optical is not None)
                     self._note_engine(self._graph_engine)
@@ -377,6 +387,7 @@ class PairPipeline:
                 return replay
 
             def replay(optical, thermal, mask_optical=None, mask_thermal=None):
+                self._check_replay_masks(mask_optical, mask_thermal)
                 with torch.cuda.device(self.device):
                     k = self._call % self.depth
                     self._call += 1
@@ -399,6 +410,14 @@ class PairPipeline:
                     self.images = self.images_b[k]
                 return self
             return replay
+
+    def _check_replay_masks(self, mask_optical, mask_thermal):
+        if (mask_optical is None) != (mask_thermal is None):
+            raise ValueError("PairPipeline replay: pass both valid masks or neither")
+        if (mask_optical is not None) != self._capture_masked:
+            raise ValueError("PairPipeline replay: the graphs were captured " + ("with" if self._capture_masked else "without") +
+                             " valid masks and this replay passes " + ("none" if self._capture_masked else "masks") +
+                             " — a replay cannot change whether the step masks; capture another pipeline for that")
 
     def _streams_of(self, k):
         return self.enc_streams if self.split_encoder else [self.enc_streams[k] if self.alternate else self.enc_stream]

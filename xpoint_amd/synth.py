@@ -396,6 +396,74 @@ def make_pair_batch(first_pair: int, batch: int, H: int, W: int):
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# non-trivial valid masks (fixture g25): pure integer constructions, no RNG.  make_pair_batch keeps
+# its all-ones masks; these replace them where a test needs masking to change the result.
+# ------------------------------------------------------------------------------------------
+
+def mask_quad(H: int, W: int) -> np.ndarray:
+    """(H, W) bool: the interior of a fixed convex perspective quad, as homographic augmentation leaves a valid mask
+    (reference homographies.py: the warped all-ones image).  Corners are integer fractions of the image size, clockwise in
+    (x, y); a pixel is valid iff it is on the inner side of (or on) all four edges, by exact integer cross products."""
+    corners = [(W * 3 // 64, H * 2 // 64), (W * 61 // 64, H * 5 // 64), (W * 59 // 64, H * 60 // 64), (W * 2 // 64, H * 57 // 64)]
+    y, x = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+    m = np.ones((H, W), dtype=bool)
+    for (x0, y0), (x1, y1) in zip(corners, corners[1:] + corners[:1]):
+        m &= (x1 - x0) * (y - y0) - (y1 - y0) * (x - x0) >= 0
+    return m
+
+
+def mask_frame(H: int, W: int, top: int, right: int, bottom: int, left: int) -> np.ndarray:
+    """(H, W) bool: all ones except a border frame of the given widths."""
+    m = np.zeros((H, W), dtype=bool)
+    m[top:H - bottom, left:W - right] = True
+    return m
+
+
+def mask_frame_hole_islands(H: int, W: int) -> np.ndarray:
+    """(H, W) bool: a frame (widths H/40 .. W/40), a rectangular hole, and isolated single valid pixels inside both the
+    frame and the hole (each one's 8 neighbours are invalid)."""
+    m = mask_frame(H, W, H // 40, W // 40, H // 40, W // 40)
+    hy, hx, hh, hw = H // 3, W // 4, H // 4, W // 3
+    m[hy:hy + hh, hx:hx + hw] = False
+    islands = [(1, W // 5), (H // 80, W // 2 + 3), (H - 2, W // 3), (H // 2, 1), (H // 3 - 1 + H // 8, W - 2),
+               (hy + 2, hx + 2), (hy + hh // 2, hx + hw // 2), (hy + hh - 3, hx + hw // 3), (hy + hh // 3, hx + hw - 4)]
+    for (y, x) in islands:
+        m[y, x] = True
+    return m
+
+
+def mask_punched(H: int, W: int, centres, half: int = 2) -> np.ndarray:
+    """(H, W) bool: all ones minus (2 half + 1)^2 squares centred on the integer (y, x) `centres` (clipped at the border)."""
+    m = np.ones((H, W), dtype=bool)
+    for (y, x) in np.asarray(centres, dtype=np.int64).reshape(-1, 2):
+        m[max(0, y - half):y + half + 1, max(0, x - half):x + half + 1] = False
+    return m
+
+
+def g25_masks(kind: int, H: int, W: int):
+    """(optical, thermal) (H, W) bool valid masks of fixture g25's pairs 0..2 (pair 3's masks depend on the reference's
+    detections and are stored in the fixture):  0 = perspective quad / uneven frame 3, 5, 7, 9 px;  1 = frame + hole +
+    islands / all ones;  2 = all zeros / all ones."""
+    ones = np.ones((H, W), dtype=bool)
+    if kind == 0:
+        return mask_quad(H, W), mask_frame(H, W, 3, 5, 7, 9)
+    if kind == 1:
+        return mask_frame_hole_islands(H, W), ones
+    if kind == 2:
+        return np.zeros((H, W), dtype=bool), ones
+    raise ValueError(f"g25_masks: no builder for kind {kind}")
+
+
+def with_masks(data, mask_optical, mask_thermal):
+    """The `make_pair_batch` dict with its valid masks replaced: mask_* (B, H, W) or (B, 1, H, W) bool (a copy; `data` is left unchanged)."""
+    out = {s: dict(v) for s, v in data.items()}
+    for spec, m in (("optical", mask_optical), ("thermal", mask_thermal)):
+        m = np.asarray(m, dtype=bool)
+        out[spec]["valid_mask"] = np.ascontiguousarray(m.reshape(out[spec]["image"].shape))
+    return out
+
+
 def to_torch(data, device="cpu"):
     import torch
     if isinstance(data, dict):

@@ -302,7 +302,7 @@ def find_homography(src_pts, dst_pts, reproj_threshold=3.0, max_iters=10000, see
 
 
 # ---------------------------------------------------------------- image registration output
-def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, dst_channels=None):
+def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, dst_channels=None, mask=None):
     """cv2.warpPerspective(img, M, dsize, flags=INTER_LINEAR [| WARP_INVERSE_MAP], borderMode=BORDER_CONSTANT) on the device
     (reference predict_align_image_pair.py:308, demo.py:225-249).
 
@@ -311,7 +311,9 @@ def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, d
     — numpy, or a float64 device tensor such as `find_homography_batched` returns (no host round trip); dsize = (width, height)
     as in cv2 (default: the source size).  quantise_u8: a float32 image in [0, 1] is quantised on load exactly as the reference
     builds `im_optical` ((np.clip(img, 0, 1) * 255.0).astype(np.uint8)) and the result is uint8; dst_channels=3 replicates a
-    one-channel source (cv2.COLOR_GRAY2RGB ahead of the warp).  Returns a device tensor shaped like the input with (Hd, Wd).
+    one-channel source (cv2.COLOR_GRAY2RGB ahead of the warp).  mask (quantise_u8 only): the source's valid mask, a bool / uint8 device
+    tensor of B x H x W elements (nonzero = valid); the image is multiplied by it before the quantisation, as the reference's
+    `optical *= mask_optical` (predict_align_image_pair.py:267) — the image itself is not modified.  Returns a device tensor shaped like the input with (Hd, Wd).
     Arithmetic: OpenCV's documented 1/32-pixel fixed-point scheme (include/xpoint_hip.h: xp_warp_perspective; parity unpinned)."""
     import numpy as np
     if not (torch.is_tensor(img) and img.is_cuda):
@@ -320,6 +322,8 @@ def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, d
         raise ValueError(f"warp_perspective: uint8 or float32 images, got {img.dtype}")
     if quantise_u8 and img.dtype != torch.float32:
         raise ValueError("warp_perspective: quantise_u8 applies to float32 images")
+    if mask is not None and not quantise_u8:
+        raise ValueError("warp_perspective: a valid mask applies with quantise_u8=True only")
     x = img
     shape_kind = x.dim()
     nchw1 = x.dim() == 4 and x.shape[1] == 1 and x.shape[3] > 4
@@ -348,9 +352,15 @@ def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, d
     u8_out = x.dtype == torch.uint8 or quantise_u8
     out = torch.empty((B, Hd, Wd, Cd), dtype=torch.uint8 if u8_out else torch.float32, device=x.device)
     dtype = 0 if x.dtype == torch.uint8 else (2 if quantise_u8 else 1)
+    mk = None
+    if mask is not None:
+        if not (torch.is_tensor(mask) and mask.device == x.device and mask.dtype in (torch.bool, torch.uint8) and mask.numel() == B * Hs * Ws):
+            raise ValueError(f"warp_perspective: the mask must be a bool / uint8 tensor of {B} x {Hs} x {Ws} elements on {x.device}")
+        mk = mask.contiguous().view(torch.uint8)
     with torch.cuda.device(x.device):
-        _lib.call("xp_warp_perspective", ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(Md.data_ptr()),
-                  B, Hs, Ws, Hd, Wd, C, Cd, dtype, 1 if inverse_map else 0, _lib.current_stream(x.device))
+        _lib.call("xp_warp_perspective_masked", ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(mk.data_ptr()) if mk is not None else None,
+                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(Md.data_ptr()), B, Hs, Ws, Hd, Wd, C, Cd, dtype, 1 if inverse_map else 0,
+                  _lib.current_stream(x.device))
     if shape_kind == 2:
         return out[0, :, :, 0] if Cd == 1 else out[0]
     if shape_kind == 3:
