@@ -238,6 +238,34 @@ def test_chunking_is_bit_identical(gpu_lib, golden, case):
             assert torch.equal(res[k], base[k]), (case, chunk, k)
 
 
+@pytest.mark.parametrize("gemm_mode", ["x3", "f32", "amp16f"])
+@pytest.mark.parametrize("case", ["ms_window", "sh_single"])
+def test_chunking_is_bit_identical_every_class(gpu_lib, golden, case, gemm_mode):
+    """test_chunking_is_bit_identical's recipe in the split-bf16, exact-f32 and half-storage classes: the views go through the forward `chunk` at a
+    time, so the aggregated maps rest on the model's batch invariance in the class it runs."""
+    g = golden("g24_homographic_adaptation.npz")
+    c = json.loads(str(g[f"{case}/config"]))
+    net = _net(c["model"])
+    assert isinstance(net, models.XPoint)
+    num = c["ha"]["num"]
+    prev = net.gemm_mode                     # the nets are shared with the other tests of this module
+    try:
+        net.gemm_mode = gemm_mode
+        base = None
+        for chunk in (1, 2, num - 1, None):
+            _, maps, count = _run_case(g, case, chunk)
+            assert net.effective_gemm_mode() == gemm_mode
+            res = {k: v.cpu() for k, v in maps.items()}
+            res["count"] = count.cpu()
+            if base is None:
+                base = res
+                continue
+            for k in base:
+                assert torch.equal(res[k], base[k]), (case, gemm_mode, chunk, k)
+    finally:
+        net.gemm_mode = prev
+
+
 def test_cli_export_equals_the_library_call(gpu_lib, tmp_path):
     from PIL import Image
     from xpoint_amd import cli

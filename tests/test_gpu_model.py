@@ -378,6 +378,41 @@ def test_batch_invariance_480x640(gpu_lib):
     assert torch.equal(o8["prob"][0], o["prob"][0]) and torch.equal(t8["desc"][0], t["desc"][0]) and torch.equal(o8["encoder_output"][0], o["encoder_output"][0])
 
 
+@pytest.mark.parametrize("gemm_mode", ["x3", "f32", "x2", "bf16", "amp16", "amp16f"])
+def test_batch_invariance_480x640_every_class(gpu_lib, gemm_mode):
+    """test_batch_invariance_480x640's recipe in every other precision class: pair 0 alone, inside the batch of 8 on the overlapped
+    alternating-encoder schedule, with the encoder split into two image groups, and through the eager forward of one and of eight pairs — prob, the
+    descriptor volume, keypoints, sampled descriptors and match indices bit-identical.  Every class runs its own dense kernels (split-bf16 at 6 / 3 / 1
+    products, exact-f32 MFMA, the fp16-rounded autocast recipe, the half-storage forward), each with row-count choices of its own."""
+    from xpoint_amd.predict import PairPipeline
+    H, W = 480, 640
+    net = _net(synth.xpoint_exp1_config(H, W))
+    net.gemm_mode = gemm_mode
+    d8, d1 = _data(0, 8, H, W), _data(0, 1, H, W)
+    args = lambda d: (d["optical"]["image"], d["thermal"]["image"], d["optical"]["valid_mask"], d["thermal"]["valid_mask"])
+    with torch.no_grad():
+        runs = {}
+        for name, B, d, kw in (("alone", 1, d1, dict()), ("batch8", 8, d8, dict(overlap=True, alternate_encoders=True)),
+                               ("split2", 8, d8, dict(overlap=True, split_encoder=2))):
+            pipe = PairPipeline(net, B, H, W, cap=8192, **kw)
+            for _ in range(2):
+                pipe.run(*args(d))
+            got = pipe.fetch()[0]
+            runs[name] = dict(prob=pipe.raw["prob"][[0, B]].clone(), desc=pipe.raw["desc_nhwc"][[0, B]].clone(), **got)
+        o, t, _ = net(d1)
+        o8, t8, _ = net(d8)
+    assert net.effective_gemm_mode() == gemm_mode
+    ref = runs["alone"]
+    assert len(ref["kp_optical"]) > 100 and len(ref["match_q"]) > 10
+    for name, r in runs.items():
+        for k in ("prob", "desc", "kp_optical", "kp_thermal", "desc_optical", "desc_thermal"):
+            assert torch.equal(r[k], ref[k]), (gemm_mode, name, k, float((r[k].float() - ref[k].float()).abs().max()) if r[k].shape == ref[k].shape else "shape")
+        assert r["match_q"].tolist() == ref["match_q"].tolist() and r["match_t"].tolist() == ref["match_t"].tolist(), (gemm_mode, name)
+    assert torch.equal(o["prob"][0, 0], ref["prob"][0]) and torch.equal(t["prob"][0, 0], ref["prob"][1])
+    for k in ("prob", "desc", "encoder_output"):
+        assert torch.equal(o8[k][0], o[k][0]) and torch.equal(t8[k][0], t[k][0]), (gemm_mode, k)
+
+
 def test_pipeline_edge_cases(gpu_lib):
     """Empty inputs (everything masked), capacity overflow and an under-iterated async NMS are detected, not silent."""
     from xpoint_amd.predict import PairPipeline

@@ -72,7 +72,9 @@ def test_split_activations_p32_layout(gpu_lib):
                                            (260, 512, 32, 3, False)])
 def test_gemm_nt_h2s_vs_fp64_and_h2_bits(gpu_lib, M, N, K, act, res):
     """within 2e-5 of fp64; where xp_gemm_nt_h2 runs its tile kernel (K < 768 or N < 384: the ping-pong h2p form sums even and odd slabs apart) the
-    two engines agree bit for bit; every tile shape of the ring engine gives the same bits (XP_RING_TILE is read once: checked by tools/ring_bench)."""
+    two engines agree bit for bit; every tile shape of the ring engine gives the same bits (XP_RING_TILE is read once: checked in child processes by
+    tests/test_gpu_batch_invariance.py::test_forced_variants_against_fp64_and_default_bits, and across the dispatch's own M thresholds by
+    test_gemm_straddles_are_bit_identical[h2s-p6])."""
     L = _lib()
     A = _u(f"rA{M}{N}{K}", (M, K)); Wt = _u(f"rW{M}{N}{K}", (N, K), -0.1, 0.1); bias = _u(f"rb{M}{N}{K}", (N,))
     scale = _u(f"rs{M}{N}{K}", (N,), 0.5, 1.5) if act in (2, 3) else None

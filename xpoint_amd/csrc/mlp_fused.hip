@@ -597,6 +597,7 @@ int launch_mlp_np(const MlpParams& p, hipStream_t s) {
     const char* eng = H2 ? "_h2_c" : "_x3_c";
     std::string tag = std::string(MODE == 2 ? "ln_proj" : PRE ? "proj_mlp_fused" : "mlp_fused") + eng + std::to_string(C);      // one tag per kernel instance
     if (NP != 6 && !H2) tag += "_np" + std::to_string(NP);
+    if (NW == 8 && !H2) tag += "_nw8";                                                                    // XP_MLP_NW8 only
     if (by_shape) tag += "_M" + std::to_string(p.M);
     // flops = algorithmic 2*M*C*H4 per GEMM (f32-equivalent); bytes: x read twice (LN input, residual) and written once
     XpProfScope prof(tag.c_str(), s, MODE == 2 ? 2.0 * p.M * C * (double)p.Nout : 4.0 * p.M * C * (double)p.H4 + (PRE ? 2.0 * p.M * C * (double)C : 0.0),

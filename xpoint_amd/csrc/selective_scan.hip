@@ -425,6 +425,12 @@ static void launch_gen(const void* u, const void* delta, const float* A, const v
                        (const T*)Bm, (const T*)Cm, Dv, delta_bias, (OT*)out, last_state, xchunks, batch, dim, delta_dim, L, N, G, softplus, vec);
 }
 
+// d_state = 1: rows at least this long run the 8-item DPP-scan kernel, shorter ones the 4-item kernel.  Measured (tools/scan_bench.py shapes and single
+// images, 4-item vs 8-item): one image 384 x 19 200 rows 92.8 vs 52.7 us, 768 x 4 800 36.5 vs 23.1 us, 1 536 x 1 200 16.2 vs 16.1 us; 16 images
+// 6 144 x 19 200 293.2 vs 306.8 us, 12 288 x 4 800 146.5 vs 152.9 us, 24 576 x 1 200 78.2 vs 112.5 us.  Long rows: the 8-item kernel (large wins for
+// one or two images, <= 5 % lost at 16); short rows: the 4-item kernel
+constexpr int kScanV2MinLen = 4096;
+
 }  // namespace
 
 extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const float* A, const float* Bm,
@@ -440,13 +446,19 @@ extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const f
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
     const bool vec = (seqlen % 4 == 0) && ((((uintptr_t)u | (uintptr_t)delta | (uintptr_t)Bm | (uintptr_t)Cm | (uintptr_t)out) & 15) == 0);
-    XpProfScope prof("selective_scan_fwd", s, (9.0 * dstate + 1.0) * batch * dim * (double)seqlen,
-                     12.0 * batch * dim * (double)seqlen + 8.0 * batch * ngroups * dstate * (double)seqlen);
     // d_state = 1: both kernels are VALU-co-limited (52 VALU + 4 transcendentals per element, 70 % VALU-busy at 4.5 TB/s); the 8-item
     // DPP-scan kernel wins where few rows leave the SIMDs under-occupied (long rows, small batch: 3.9 vs 3.3 TB/s at 1536 rows x 65536),
-    // the 4-item kernel where >= 3 waves per SIMD hide its LDS-crossbar scan (XP_SCAN_V1 / XP_SCAN_V2 force one for A/B runs)
+    // the 4-item kernel where >= 3 waves per SIMD hide its LDS-crossbar scan (XP_SCAN_V1 / XP_SCAN_V2 force one for A/B runs).
+    // The two kernels associate the scan differently and so differ in the last bits: the choice is made from seqlen only, never from batch * dim,
+    // so a row's output does not depend on the other rows of the call (tests/test_gpu_batch_invariance.py).
     static const bool v1 = getenv("XP_SCAN_V1") != nullptr, v2 = getenv("XP_SCAN_V2") != nullptr;
-    const bool use_v2 = v2 || (!v1 && rows < 3072 && seqlen >= 1024);
+    const bool use_v2 = v2 || (!v1 && seqlen >= kScanV2MinLen);
+    static const bool old_gen = getenv("XP_SCAN_OLD_GEN") != nullptr;
+    // one profiling tag per kernel, so a test can tell which one ran
+    const char* tag = dstate == 1 ? (!vec ? "selective_scan_fwd_n1s" : use_v2 ? "selective_scan_fwd_n1v2" : "selective_scan_fwd_n1")
+                                  : (old_gen ? "selective_scan_fwd_old" : "selective_scan_fwd_gen");
+    XpProfScope prof(tag, s, (9.0 * dstate + 1.0) * batch * dim * (double)seqlen,
+                     12.0 * batch * dim * (double)seqlen + 8.0 * batch * ngroups * dstate * (double)seqlen);
     if (dstate == 1) {
         if (vec && use_v2)
             hipLaunchKernelGGL(selective_scan_fwd_n1v2_kernel, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state,
@@ -459,7 +471,6 @@ extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const f
                                batch, dim, delta_dim, seqlen, ngroups, delta_softplus);
     } else {
         // d_state > 1: the 8-item DPP-scan kernel (the 4-item shuffle-scan kernel above ran at 0.08 of HBM at N = 16)
-        static const bool old_gen = getenv("XP_SCAN_OLD_GEN") != nullptr;
         if (!old_gen) launch_gen<float, float, true>(u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, nullptr, batch, dim, delta_dim, seqlen, dstate, ngroups, delta_softplus, s);
         else if (vec)
             hipLaunchKernelGGL(selective_scan_fwd_kernel<true>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out,
