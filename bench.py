@@ -14,6 +14,11 @@ of 8 synthetic 480x640 optical/thermal pairs per GPU (BASELINE.json configs[1]);
 HBM when the timed region starts.  Pairs are independent units: every rank runs the full path on its
 own shard (weak scaling), the only collective is the one-time RCCL broadcast of the packed weights.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the timed regions, --dump-outputs, the line.
+`--full` adds everything else the line can carry: the per-kernel breakdown and roofline, the single-stream rate, the other dense-layer
+back ends and precision classes, the rotating-input and sustained regions, the PCIe-inclusive passes, the matcher statistics, the
+steady-state weight re-broadcasts and the CPU baseline (--no-other-backend, --no-h2d and --no-cpu-baseline switch parts of it off).
 """
 import argparse
 import json
@@ -50,7 +55,8 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2", help="BASELINE.json configuration (c2 = the headline; c4, c5: see CONFIGS)")
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU per step (default: the configuration's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline (see the module docstring); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--regions", type=int, default=5, help="the K-step timed region is run this many times inside one invocation; `value` is the MEDIAN "
                                                             "region (a single 20-step region is 0.1 s: +-5 % run to run); every region is listed in the line")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="unwrapped --gpus N > 1: seconds the parent waits for the child job before "
@@ -79,6 +85,9 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run measures the headline alone: the extra passes and the CPU baseline are --full's
+        args.no_other_backend = args.no_h2d = args.no_cpu_baseline = True
     return args
 
 
@@ -494,7 +503,8 @@ def main():
         rccl["weight_blob_mb"] = round(blob.numel() * 4 / 1e6, 1)
         if xdist.last_first_broadcast_ms is not None:
             rccl["weight_bcast_first_ms"] = round(xdist.last_first_broadcast_ms, 3)          # the job's first collective: includes RCCL's lazy set-up
-        rccl["weight_bcast_ms"] = round(xdist.timed_broadcast(blob, src=0, repeats=5), 3)   # steady-state re-broadcasts of the same blob
+        if args.full:
+            rccl["weight_bcast_ms"] = round(xdist.timed_broadcast(blob, src=0, repeats=5), 3)   # steady-state re-broadcasts of the same blob
 
     B = args.pairs
     first, _ = xdist.shard_pairs(world * B, world, rank)   # every rank owns its own contiguous block of pairs
@@ -507,9 +517,9 @@ def main():
     sweeps = conf.get("nms_sweeps", 8)       # sweeps past the fixed point exit at once; 1024x1024 needs more than 480x640 (longer suppression chains)
     pipe = PairPipeline(net, B, H, W, cap=CAP, cfg_prediction=pred, nms_sweeps=sweeps, overlap=overlap, split_encoder=args.split_encoder,
                         estimate_homography=args.register, alternate_encoders=(int(os.environ.get("XP_BENCH_DEPTH", "3")) if not args.no_alternate and args.split_encoder in (0, 1) else 0))
-    # single-stream twin for the per-kernel measurements: with several streams in flight a launch's HIP-event duration
+    # single-stream twin for the per-kernel measurements (--full): with several streams in flight a launch's HIP-event duration
     # includes the time it shares the GPU with other kernels, which says nothing about the kernel itself
-    pipe1 = PairPipeline(net, B, H, W, cap=CAP, cfg_prediction=pred, nms_sweeps=sweeps, estimate_homography=args.register) if overlap else pipe
+    pipe1 = PairPipeline(net, B, H, W, cap=CAP, cfg_prediction=pred, nms_sweeps=sweeps, estimate_homography=args.register) if overlap and args.full else pipe
     # config c5: the homography-regression head on the 256x256 crops (a second, small forward through the same encoder weights)
     net_hm = None
     if args.config == "c5":
@@ -543,20 +553,26 @@ def main():
             pipe.run(opt, thr, mo, mt)
         torch.cuda.synchronize()
         pipe.verify()
-        # one untimed single-stream pass with every kernel bracketed by HIP events: per-kernel breakdown, picks the dominant kernel
-        pipe1.run(opt, thr, mo, mt); torch.cuda.synchronize()
-        lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
-        pipe1.run(opt, thr, mo, mt)
-        torch.cuda.synchronize()
-        lib.xp_prof_enable(0)
-        breakdown = sorted(prof_table(), key=lambda r: -r["ms"])
-        dominant = breakdown[0]["tag"]
-        if args.graph:
-            # HIP events cannot be recorded inside a replayed graph: the dominant kernel is timed in eager single-stream passes first
+        if args.full:
+            # one untimed single-stream pass with every kernel bracketed by HIP events: per-kernel breakdown, picks the dominant kernel
+            pipe1.run(opt, thr, mo, mt); torch.cuda.synchronize()
+            lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
+            pipe1.run(opt, thr, mo, mt)
+            torch.cuda.synchronize()
+            lib.xp_prof_enable(0)
+            breakdown = sorted(prof_table(), key=lambda r: -r["ms"])
+            dominant = breakdown[0]["tag"]
+
+        def time_dominant_single_stream():
+            """--full: the dominant kernel's launches timed in 3 eager single-stream passes (same data, same kernels) next to the timed region"""
             lib.xp_prof_reset(); lib.xp_prof_filter(dominant.encode()); lib.xp_prof_enable(1)
             for _ in range(3):
                 pipe1.run(opt, thr, mo, mt)
             torch.cuda.synchronize(); lib.xp_prof_enable(0)
+
+        if args.graph:
+            if args.full:
+                time_dominant_single_stream()           # HIP events cannot be recorded inside a replayed graph
             if args.config == "c5":
                 # streaming step (xpoint_amd/streaming.py; tests/test_gpu_configs.py checks the same object against the reference fixtures): images
                 # from pinned host memory straight into the batch buffers, graphs replayed, RegNet head on the 256x256 crops from its own graph,
@@ -579,17 +595,14 @@ def main():
             torch.cuda.synchronize()
         elif overlap:
             step = lambda: pipe.run(opt, thr, mo, mt)
-            # the dominant kernel's launches are timed in single-stream passes right here (same data, same kernels);
-            # the timed region below runs without any events
-            lib.xp_prof_reset(); lib.xp_prof_filter(dominant.encode()); lib.xp_prof_enable(1)
-            for _ in range(3):
-                pipe1.run(opt, thr, mo, mt)
-            torch.cuda.synchronize(); lib.xp_prof_enable(0)
-            pipe.run(opt, thr, mo, mt)
+            if args.full:
+                time_dominant_single_stream()           # the timed region below runs without any events
+            pipe.run(opt, thr, mo, mt)                  # one more untimed step: with or without --full the timed region starts from the same pipeline state
         else:
             step = lambda: pipe.run(opt, thr, mo, mt)
-            # timed region: only the dominant kernel's launches carry events (on their launch stream)
-            lib.xp_prof_reset(); lib.xp_prof_filter(dominant.encode()); lib.xp_prof_enable(1)
+            if args.full:
+                # timed region: only the dominant kernel's launches carry events (on their launch stream)
+                lib.xp_prof_reset(); lib.xp_prof_filter(dominant.encode()); lib.xp_prof_enable(1)
         # the timed region: K steps bracketed by barrier + synchronize on both sides, run `--regions` times back to back; the line reports the
         # MEDIAN region (max over ranks per region) and lists them all.  steps = K stays what one region times.
         region_dt = []
@@ -600,8 +613,9 @@ def main():
                 step()
             sync_all()
             region_dt.append(time.perf_counter() - t0)
-        lib.xp_prof_enable(0)
-        dom = [r for r in prof_table() if r["tag"] == dominant][0]
+        if args.full:
+            lib.xp_prof_enable(0)
+            dom = [r for r in prof_table() if r["tag"] == dominant][0]
         pipe.verify()
         if args.config == "c5":
             sstep.verify()                  # the head's own status word (its forward runs from its own graph): read once, after the timed region
@@ -704,11 +718,12 @@ def main():
                                            "note": "one timed region of >= 10 s on the headline schedule (same batch every step), shader clock from sysfs pp_dpm_sclk / rocm-smi"}
             pipe.run(opt, thr, mo, mt)
             torch.cuda.synchronize()
-    ms = pipe.match_stats()
-    hygiene["match_candidates_per_row"] = {"mean": ms["mean"], "max": ms["max"]}
-    hygiene["match_overflow_rows"] = ms["overflow_rows"]
-    hygiene["match_stats_note"] = (f"nomination lists of the last step's matcher call over {ms['rows']} live rows + columns (inline capacity {ms['inline_capacity']}; longer lists "
-                                   "go through the parallel overflow pass): the matcher's time depends on them, its result never does")
+    if args.full:
+        ms = pipe.match_stats()
+        hygiene["match_candidates_per_row"] = {"mean": ms["mean"], "max": ms["max"]}
+        hygiene["match_overflow_rows"] = ms["overflow_rows"]
+        hygiene["match_stats_note"] = (f"nomination lists of the last step's matcher call over {ms['rows']} live rows + columns (inline capacity {ms['inline_capacity']}; "
+                                       "longer lists go through the parallel overflow pass): the matcher's time depends on them, its result never does")
     pcie = None
     pcie_u8 = None
     if not args.no_h2d and args.config == "c2":
@@ -776,45 +791,46 @@ def main():
         rccl["rank_headers"] = [dict(rank=i, first_pair=h[0], pairs=h[1], keypoints=h[2], matches=h[3]) for i, h in enumerate(hdr)]
 
     if rank == 0:
-        avg_s = dom["ms"] / max(dom["launches"], 1) * 1e-3
-        if dom["flops"] > 0 and dominant.startswith(("gemm", "conv3x3", "mlp_fused", "proj_mlp_fused")):
-            ach = dom["flops"] / dom["launches"] / avg_s / 1e12
-            x3 = "_x3" in dominant or "_h2" in dominant or "_f16" in dominant          # ("_h2" also matches the _h2r / _h2p schedules: same three-product arithmetic)
-            nprod = 1 if "_f16" in dominant else (H2_PRODUCTS if "_h2" in dominant else X3_PRODUCTS)
-            # split kernels: algorithmic (f32-equivalent) 2MNK flops against the 16-bit dense MFMA peak / partial products per multiply
-            peak = MFMA_BF16_PEAK_TFLOPS / nprod if x3 else MFMA_F32_PEAK_TFLOPS
-            roof = {"kernel": dominant, "bound": "mfma", "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                    "frac": round(ach / peak, 4), "traffic": None,
-                    "algorithmic_gflop_per_launch": round(dom["flops"] / dom["launches"] / 1e9, 3)}
-            roof["frac_vs_f32_matrix_peak"] = round(ach / MFMA_F32_PEAK_TFLOPS, 4)      # orientation only: algorithmic flops against the exact-f32 MFMA peak
-            if x3:
-                roof["peak_note"] = (f"f32-equivalent: bf16 / fp16 dense MFMA peak {MFMA_BF16_PEAK_TFLOPS:.0f} TFLOP/s / {nprod} partial products per "
-                                     f"f32-grade multiply; executed 16-bit MFMA rate = {ach * nprod:.0f} TFLOP/s = {ach * nprod / MFMA_BF16_PEAK_TFLOPS:.3f} of peak")
-        else:
-            ach = dom["bytes"] / dom["launches"] / avg_s / 1e9
-            roof = {"kernel": dominant, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                    "algorithmic_mb_per_launch": round(dom["bytes"] / dom["launches"] / 1e6, 3)}
-        roof.update(pmc_fields(dominant, roof["bound"], args.config, args.precision_class))
-        if dominant.startswith("gemm_ring"):
-            roof["dense_engine_ceilings"] = dense_engine_ceilings()
-        roof.update({"avg_launch_us": round(avg_s * 1e6, 2), "launches_timed": dom["launches"]})
-        if overlap or args.graph:
-            roof["measured_in"] = ("3 single-stream eager passes of the same step next to the timed region: " +
-                                   ("HIP events cannot be recorded inside a replayed graph" if args.graph else
-                                    "in the timed region kernels of several streams run concurrently, so a launch's event duration includes time-sharing"))
-        else:
-            roof["share_of_step"] = round(dom["ms"] / (dt * 1e3), 4)
-        tot = sum(r["ms"] for r in breakdown)
-        sys.stderr.write("per-kernel breakdown of one step (HIP events, untimed pass):\n")
-        for r in breakdown:
-            extra = ""
-            if r["flops"] > 0 and r["ms"] > 0:
-                extra += f"  {r['flops'] / r['ms'] / 1e9:8.1f} TFLOP/s"
-            if r["bytes"] > 0 and r["ms"] > 0:
-                extra += f"  {r['bytes'] / r['ms'] / 1e6:8.1f} GB/s"
-            sys.stderr.write(f"  {r['tag']:28s} {r['ms']:8.3f} ms {100 * r['ms'] / tot:5.1f}%  x{r['launches']:3d}{extra}\n")
-        sys.stderr.write(f"  {'sum':28s} {tot:8.3f} ms\n")
+        if args.full:
+            avg_s = dom["ms"] / max(dom["launches"], 1) * 1e-3
+            if dom["flops"] > 0 and dominant.startswith(("gemm", "conv3x3", "mlp_fused", "proj_mlp_fused")):
+                ach = dom["flops"] / dom["launches"] / avg_s / 1e12
+                x3 = "_x3" in dominant or "_h2" in dominant or "_f16" in dominant          # ("_h2" also matches the _h2r / _h2p schedules: same three-product arithmetic)
+                nprod = 1 if "_f16" in dominant else (H2_PRODUCTS if "_h2" in dominant else X3_PRODUCTS)
+                # split kernels: algorithmic (f32-equivalent) 2MNK flops against the 16-bit dense MFMA peak / partial products per multiply
+                peak = MFMA_BF16_PEAK_TFLOPS / nprod if x3 else MFMA_F32_PEAK_TFLOPS
+                roof = {"kernel": dominant, "bound": "mfma", "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                        "frac": round(ach / peak, 4), "traffic": None,
+                        "algorithmic_gflop_per_launch": round(dom["flops"] / dom["launches"] / 1e9, 3)}
+                roof["frac_vs_f32_matrix_peak"] = round(ach / MFMA_F32_PEAK_TFLOPS, 4)      # orientation only: algorithmic flops against the exact-f32 MFMA peak
+                if x3:
+                    roof["peak_note"] = (f"f32-equivalent: bf16 / fp16 dense MFMA peak {MFMA_BF16_PEAK_TFLOPS:.0f} TFLOP/s / {nprod} partial products per "
+                                         f"f32-grade multiply; executed 16-bit MFMA rate = {ach * nprod:.0f} TFLOP/s = {ach * nprod / MFMA_BF16_PEAK_TFLOPS:.3f} of peak")
+            else:
+                ach = dom["bytes"] / dom["launches"] / avg_s / 1e9
+                roof = {"kernel": dominant, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                        "algorithmic_mb_per_launch": round(dom["bytes"] / dom["launches"] / 1e6, 3)}
+            roof.update(pmc_fields(dominant, roof["bound"], args.config, args.precision_class))
+            if dominant.startswith("gemm_ring"):
+                roof["dense_engine_ceilings"] = dense_engine_ceilings()
+            roof.update({"avg_launch_us": round(avg_s * 1e6, 2), "launches_timed": dom["launches"]})
+            if overlap or args.graph:
+                roof["measured_in"] = ("3 single-stream eager passes of the same step next to the timed region: " +
+                                       ("HIP events cannot be recorded inside a replayed graph" if args.graph else
+                                        "in the timed region kernels of several streams run concurrently, so a launch's event duration includes time-sharing"))
+            else:
+                roof["share_of_step"] = round(dom["ms"] / (dt * 1e3), 4)
+            tot = sum(r["ms"] for r in breakdown)
+            sys.stderr.write("per-kernel breakdown of one step (HIP events, untimed pass):\n")
+            for r in breakdown:
+                extra = ""
+                if r["flops"] > 0 and r["ms"] > 0:
+                    extra += f"  {r['flops'] / r['ms'] / 1e9:8.1f} TFLOP/s"
+                if r["bytes"] > 0 and r["ms"] > 0:
+                    extra += f"  {r['bytes'] / r['ms'] / 1e6:8.1f} GB/s"
+                sys.stderr.write(f"  {r['tag']:28s} {r['ms']:8.3f} ms {100 * r['ms'] / tot:5.1f}%  x{r['launches']:3d}{extra}\n")
+            sys.stderr.write(f"  {'sum':28s} {tot:8.3f} ms\n")
         out = {
             "metric": "image-pairs/sec (detect+describe+match) 480x640 optical-thermal" + ("" if args.precision_class == "f32" else f" [NOT the headline: precision class {args.precision_class}]"),
             "value": round(world * B * args.steps / dt, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
@@ -836,7 +852,6 @@ def main():
                                           "step i's detection / matching kernels; all K steps complete inside the timed region") if overlap else "none (one stream)",
                        "keypoints_per_image_mean": round(sum(len(r["kp_optical"]) + len(r["kp_thermal"]) for r in res) / (2 * len(res)), 1),
                        "matches_per_pair_mean": round(sum(len(r["match_q"]) for r in res) / len(res), 1)},
-            "roofline": roof,
             "timed_regions": {"count": len(job_dt), "reported": "median", "pairs_per_s": [round(world * B * args.steps / t, 2) for t in job_dt],
                               "note": f"{len(job_dt)} regions of K = {args.steps} steps each (barrier + synchronize on both sides, max over ranks), back to back in this invocation"},
             "per_rank_pairs_per_s": {"min": round(min(rank_rates), 2), "max": round(max(rank_rates), 2),
@@ -846,25 +861,27 @@ def main():
         out.update(hygiene)
         out["rank_cpu_affinity"] = {"rank0": pin, "cpus_per_rank": rank_cpus, "note": "every rank pins itself (os.sched_setaffinity before torch is imported) to the CPUs of its GPU's NUMA node, "
                                                            "GPUs on one node splitting them (xpoint_amd/affinity.py); the CPU baseline runs on the unpinned mask"}
-        # the other large kernels of the step, each against its own bound (from the untimed single-stream breakdown pass; the
-        # `roofline` object above is the dominant one, timed next to the timed region)
-        tot_ms = sum(r["ms"] for r in breakdown) or 1.0
-        top = []
-        for r in breakdown[:8]:
-            if r["ms"] <= 0 or r["launches"] <= 0:
-                continue
-            mfma = r["flops"] > 0 and r["tag"].startswith(("gemm", "conv3x3", "mlp_fused", "proj_mlp_fused", "ln_proj"))
-            if mfma:
-                x3k = "_x3" in r["tag"] or "_h2" in r["tag"] or "_f16" in r["tag"]
-                pk = MFMA_BF16_PEAK_TFLOPS / (1 if "_f16" in r["tag"] else H2_PRODUCTS if "_h2" in r["tag"] else X3_PRODUCTS) if x3k else MFMA_F32_PEAK_TFLOPS
-                a = r["flops"] / r["ms"] / 1e9
-                top.append({"kernel": r["tag"], "bound": "mfma", "achieved": round(a, 1), "peak": round(pk, 1), "unit": "TFLOP/s",
-                            "frac": round(a / pk, 4), "share_of_single_stream_step": round(r["ms"] / tot_ms, 4), "launches": r["launches"]})
-            elif r["bytes"] > 0:
-                a = r["bytes"] / r["ms"] / 1e6
-                top.append({"kernel": r["tag"], "bound": "hbm", "achieved": round(a, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": round(a / HBM_PEAK_GBS, 4), "share_of_single_stream_step": round(r["ms"] / tot_ms, 4), "launches": r["launches"]})
-        out["roofline_top_kernels"] = top
+        if args.full:
+            out["roofline"] = roof
+            # the other large kernels of the step, each against its own bound (from the untimed single-stream breakdown pass; the
+            # `roofline` object above is the dominant one, timed next to the timed region)
+            tot_ms = sum(r["ms"] for r in breakdown) or 1.0
+            top = []
+            for r in breakdown[:8]:
+                if r["ms"] <= 0 or r["launches"] <= 0:
+                    continue
+                mfma = r["flops"] > 0 and r["tag"].startswith(("gemm", "conv3x3", "mlp_fused", "proj_mlp_fused", "ln_proj"))
+                if mfma:
+                    x3k = "_x3" in r["tag"] or "_h2" in r["tag"] or "_f16" in r["tag"]
+                    pk = MFMA_BF16_PEAK_TFLOPS / (1 if "_f16" in r["tag"] else H2_PRODUCTS if "_h2" in r["tag"] else X3_PRODUCTS) if x3k else MFMA_F32_PEAK_TFLOPS
+                    a = r["flops"] / r["ms"] / 1e9
+                    top.append({"kernel": r["tag"], "bound": "mfma", "achieved": round(a, 1), "peak": round(pk, 1), "unit": "TFLOP/s",
+                                "frac": round(a / pk, 4), "share_of_single_stream_step": round(r["ms"] / tot_ms, 4), "launches": r["launches"]})
+                elif r["bytes"] > 0:
+                    a = r["bytes"] / r["ms"] / 1e6
+                    top.append({"kernel": r["tag"], "bound": "hbm", "achieved": round(a, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(a / HBM_PEAK_GBS, 4), "share_of_single_stream_step": round(r["ms"] / tot_ms, 4), "launches": r["launches"]})
+            out["roofline_top_kernels"] = top
         if single_rate is not None:
             out["single_stream"] = {"pairs_per_s": round(single_rate, 2), "note": "same steps enqueued on one HIP stream (bench.py --no-overlap)"}
         if other_rate is not None:

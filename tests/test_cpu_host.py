@@ -332,3 +332,20 @@ def test_bench_dump_outputs_layout_budget_and_stable_sample(tmp_path):
     keep = set(map(tuple, kp[sel0]))
     sel1 = bench.desc_sample_rows(kp[1:], frac)
     assert set(map(tuple, kp[1:][sel1])) == keep - {tuple(kp[0])}
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """bench.py without --full measures the headline alone: the extra passes, the PCIe-inclusive regions and the CPU baseline are off whatever
+    else is given; --full turns them on, and its --no-* options still switch single ones off."""
+    import importlib, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    extras = ("no_other_backend", "no_h2d", "no_cpu_baseline")
+    for argv, off in ((["--gpus", "1", "--steps", "3", "--warmup", "1"], (True, True, True)),
+                      (["--cpu-pairs", "4", "--register"], (True, True, True)),
+                      (["--full"], (False, False, False)),
+                      (["--full", "--no-h2d"], (False, True, False))):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        args = bench.parse()
+        assert args.full == ("--full" in argv) and tuple(getattr(args, k) for k in extras) == off, (argv, vars(args))

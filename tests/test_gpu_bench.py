@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 import torch
@@ -24,7 +25,7 @@ def _run(n, extra=()):
 def test_bench_launcher_rccl_world():
     world = min(2, torch.cuda.device_count())
     assert world >= 1
-    r = _run(world)
+    r = _run(world, ("--full",))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -70,7 +71,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     regions / CPU masks / result headers, max-over-ranks timing, ONE JSON line with every key of the 1-GPU line.  Rates of this run mean nothing."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["XP_BENCH_REHEARSE_ON_ONE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-pairs", "1", "--no-other-backend", "--no-h2d"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--cpu-pairs", "1", "--no-other-backend", "--no-h2d"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -91,10 +92,10 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
 
 
 def test_bench_hygiene_keys_and_fast_class_label():
-    """The default line carries the rotating-input and sustained-region rates (with the shader clock) and the reduced-precision classes incl. amp16f; a
+    """The --full line carries the rotating-input and sustained-region rates (with the shader clock) and the reduced-precision classes incl. amp16f; a
     `--precision-class amp16f` run labels itself as not the headline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["rotating_inputs_pairs_per_s"] > 0.8 * out["value"]
@@ -104,7 +105,7 @@ def test_bench_hygiene_keys_and_fast_class_label():
     cls = out["reduced_precision_classes"]["pairs_per_s"]
     assert cls["amp16f"] > out["value"] and cls["amp16f"] > cls["amp16"], cls          # the half-storage class is the FAST one
     assert out["pcie_inclusive_pairs_per_s"] > 0.6 * out["value"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-h2d", "--precision-class", "amp16f"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-h2d", "--precision-class", "amp16f"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -141,6 +142,33 @@ def test_bench_dump_outputs(tmp_path):
         assert np.array_equal(a[f"desc_{spec}_rows"][:len(sel)], sel) and a[f"desc_{spec}"].shape == (len(a[f"desc_{spec}_rows"]), 256)
         assert np.isfinite(a[f"desc_{spec}"]).all()
     assert len(a["match_q"]) == len(a["match_t"]) == len(a["match_d"]) == counts[:, 2].sum()
+
+
+FULL_ONLY_KEYS = ("roofline", "roofline_top_kernels", "cpu_baseline", "single_stream", "other_gemm_backends", "reduced_precision_classes",
+                  "rotating_inputs_pairs_per_s", "sustained_pairs_per_s", "pcie_inclusive_pairs_per_s", "match_candidates_per_row", "weight_bcast_ms")
+
+
+def test_bench_plain_run_is_lean():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline alone: the line carries the headline keys and none of --full's, no
+    per-kernel breakdown is printed, and the whole process spends at most 30 s outside its N + W steps."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    steps, warmup = 20, 2
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, env=env, timeout=900)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"].startswith("image-pairs/sec") and out["unit"] == "pairs/s" and out["higher_is_better"] is True and out["dtype"].startswith("f32")
+    assert out["steps"] == steps and out["warmup"] == warmup and out["value"] > 0
+    assert abs(out["ms_per_step"] * out["value"] / 1e3 - 8) < 0.01 * 8            # 8 pairs per step
+    assert out["timed_regions"]["count"] == 5 and sorted(out["timed_regions"]["pairs_per_s"])[2] == pytest.approx(out["value"], rel=1e-3)
+    assert not set(FULL_ONLY_KEYS) & set(out), sorted(set(FULL_ONLY_KEYS) & set(out))
+    assert "per-kernel breakdown" not in r.stderr
+    outside = wall - (steps + warmup) * out["ms_per_step"] / 1e3
+    assert outside <= 30.0, outside
 
 
 def test_bench_launcher_refuses_more_gpus_than_visible():
