@@ -60,6 +60,30 @@ int xp_selective_scan_fwd_typed(const void* u, const void* delta, const float* A
                                 const float* delta_bias, void* out, float* x_chunks, int itype, int out_float, int batch, int dim,
                                 int delta_dim, int seqlen, int dstate, int ngroups, int delta_softplus, void* stream);
 
+/* xp_selective_scan_fwd with the per-chunk scan state of xp_selective_scan_fwd_typed as an extra output: x_chunks (batch, dim,
+ * ceil(seqlen / 2048), 2 * dstate) f32, non-NULL.  out and last_state are bit-identical to xp_selective_scan_fwd's (the same kernels; the
+ * chunk states are bookkeeping next to the scan).  The forward of the differentiable float32 selective_scan_fn. */
+int xp_selective_scan_fwd_x(const float* u, const float* delta, const float* A, const float* B, const float* C, const float* D,
+                            const float* delta_bias, float* out, float* last_state, float* x_chunks, int batch, int dim, int delta_dim,
+                            int seqlen, int dstate, int ngroups, int delta_softplus, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Selective-scan backward.  Replaces the pybind op `selective_scan_cuda_oflex.bwd(u, delta, A, B, C, D, delta_bias, dout, x,
+ * delta_softplus, nrows)` (selective_scan_oflex.cpp:233-350).  Inputs as the forward (itype 0 / 1 / 2 = f32 / f16 / bf16 u, delta, B, C;
+ * A, D, delta_bias f32); dout (batch, dim, seqlen) f32 if dout_float else the input type; x_chunks = the forward's chunk states
+ * (xp_selective_scan_fwd_typed / xp_selective_scan_fwd_x), required when seqlen > 2048 (NULL allowed otherwise: the row starts from 0).
+ * Outputs: du (batch, dim, seqlen) and ddelta (batch, delta_dim, seqlen) in the input type (ddelta summed over the delta repeat);
+ * dA (dim, dstate), dD (dim) or NULL, ddelta_bias (delta_dim) or NULL in f32; dB, dC (batch, ngroups, dstate, seqlen) accumulated in f32 and
+ * stored in the input type.  Every sum runs in a fixed order (per-workgroup partials in the workspace and a reduce pass, no atomics):
+ * two calls are bit-identical and the per-sample gradients du / ddelta / dB / dC do not depend on the other samples.
+ * workspace: xp_selective_scan_bwd_workspace_bytes(...) bytes, 256-byte aligned.  dstate 1 runs a specialised kernel. */
+size_t xp_selective_scan_bwd_workspace_bytes(int batch, int dim, int delta_dim, int seqlen, int dstate, int ngroups);
+int xp_selective_scan_bwd_typed(const void* u, const void* delta, const float* A, const void* B, const void* C, const float* D,
+                                const float* delta_bias, const void* dout, const float* x_chunks, void* du, void* ddelta, float* dA,
+                                void* dB, void* dC, float* dD, float* ddelta_bias, void* workspace, size_t workspace_bytes, int itype,
+                                int dout_float, int batch, int dim, int delta_dim, int seqlen, int dstate, int ngroups,
+                                int delta_softplus, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Stand-alone four-route cross scan / cross merge.  Replace `cross_scan_fn` / `cross_merge_fn`
  * (xpoint/models/vmamba_src/csm_triton.py:501-517; torch forms cross_scan_fwd :22-53, cross_merge_fwd :56-85, one_by_one forms :88-180;

@@ -28,6 +28,8 @@ _SIGNATURES = {
     "xp_knob_info": [c_i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)],
     "xp_selective_scan_fwd": [c_p] * 9 + [c_i] * 7 + [c_p],
     "xp_selective_scan_fwd_typed": [c_p] * 9 + [c_i] * 9 + [c_p],
+    "xp_selective_scan_fwd_x": [c_p] * 10 + [c_i] * 7 + [c_p],
+    "xp_selective_scan_bwd_typed": [c_p] * 17 + [c_sz] + [c_i] * 9 + [c_p],
     "xp_cross_scan": [c_p, c_p] + [c_i] * 9 + [c_p],
     "xp_cross_merge": [c_p, c_p] + [c_i] * 9 + [c_p],
     "xp_ss2d_core_fwd": [c_p] * 10 + [c_sz] + [c_i] * 6 + [c_f, c_p],
@@ -122,6 +124,7 @@ _SIZE_QUERIES = {
     "xp_param_count": (c_i, [c_p]),
     "xp_forward_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
     "xp_ss2d_core_workspace_bytes": (c_sz, [c_i] * 4),
+    "xp_selective_scan_bwd_workspace_bytes": (c_sz, [c_i] * 6),
     "xp_split_weights_x3_bytes": (c_sz, [c_i] * 2),
     "xp_split_weights_h2_bytes": (c_sz, [c_i] * 2),
     "xp_p32_bytes": (c_sz, [c_l, c_i]),

@@ -110,6 +110,17 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_kernel(
 }
 
 
+// d_state == 1: the optional per-2048-element chunk state x (batch, dim, ceil(L / 2048), 2) of xp_selective_scan_fwd_x -- the running product
+// of the decays and h at the end of every chunk, the layout of the general kernel's x output below.  Called after every step of `step` elements
+// starting at c0 with the step's total decay; only bookkeeping, the output arithmetic is untouched.
+__device__ __forceinline__ void xc_record(float* xchunks, int64_t row, int L, int c0, int step, int lane, float& pr, float step_a, float h) {
+    pr *= step_a;
+    if (lane == 0 && ((c0 + step) % 2048 == 0 || c0 + step >= L)) {
+        float* xp = xchunks + (row * ((L + 2047) / 2048) + c0 / 2048) * 2;
+        xp[0] = pr; xp[1] = h;
+    }
+}
+
 // d_state == 1 (the XPoint configuration), software pipelined: the four 16-byte loads of chunk c+1 are issued before the
 // arithmetic of chunk c, so a wave always has a chunk of HBM traffic in flight behind its transcendental work.
 template <bool VEC>
@@ -117,6 +128,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1_kernel(
     const float* __restrict__ u, const float* __restrict__ delta, const float* __restrict__ A,
     const float* __restrict__ Bm, const float* __restrict__ Cm, const float* __restrict__ Dv,
     const float* __restrict__ delta_bias, float* __restrict__ out, float* __restrict__ last_state,
+    float* __restrict__ xchunks,
     int batch, int dim, int delta_dim, int L, int G, int softplus) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + wave;
@@ -129,7 +141,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1_kernel(
     const float* Cp = Cm + ((int64_t)b * G + g) * L;
     float* op = out + row * L;
     const float Dval = Dv ? Dv[d] : 0.f, bias = delta_bias ? delta_bias[dd] : 0.f, An = A[d];
-    float h = 0.f;
+    float h = 0.f, pr = 1.f;
     float uv[kItems], dv[kItems], bv[kItems], cv[kItems];
     auto fetch = [&](int c0) {
         const int off = c0 + lane * kItems, rem = L - off;
@@ -169,6 +181,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1_kernel(
 #pragma unroll
         for (int i = 0; i < kItems; ++i) ov[i] = Dval * cu[i] + cc[i] * (la[i] * hin + lb[i]);
         h = __shfl(ta, 63, 64) * h + __shfl(tb, 63, 64);
+        if (xchunks) xc_record(xchunks, row, L, c0, kChunk, lane, pr, __shfl(ta, 63, 64), h);
         if (VEC && rem >= kItems) {
             *reinterpret_cast<float4*>(op + off) = make_float4(ov[0], ov[1], ov[2], ov[3]);
         } else {
@@ -207,6 +220,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1v2_kernel(
     const float* __restrict__ u, const float* __restrict__ delta, const float* __restrict__ A,
     const float* __restrict__ Bm, const float* __restrict__ Cm, const float* __restrict__ Dv,
     const float* __restrict__ delta_bias, float* __restrict__ out, float* __restrict__ last_state,
+    float* __restrict__ xchunks,
     int batch, int dim, int delta_dim, int L, int G, int softplus) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + wave;
@@ -219,7 +233,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1v2_kernel(
     const float* Cp = Cm + ((int64_t)b * G + g) * L + lane * kItems8;
     float* op = out + row * L + lane * kItems8;
     const float Dval = Dv ? Dv[d] : 0.f, bias = delta_bias ? delta_bias[dd] : 0.f, An = A[d];
-    float h = 0.f;
+    float h = 0.f, pr = 1.f;
     // one step's (a, b): delta = softplus(x) (torch threshold 20), a = exp(delta * A); below the threshold both from ONE logarithm:
     // delta = ln(1 + e^x), a = (1 + e^x)^A = 2^(A log2(1 + e^x))   (same arithmetic as step_vals in ss2d.hip)
     auto step = [&](float x, float Bu, float& a, float& bb) {
@@ -263,6 +277,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1v2_kernel(
 #pragma unroll
         for (int i = 0; i < 8; ++i) ov[i] = Dval * cu[i] + cc[i] * (la[i] * hin + lb[i]);
         h = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ta), 63)) * h + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tb), 63));
+        if (xchunks) xc_record(xchunks, row, L, c * kChunk8, kChunk8, lane, pr, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ta), 63)), h);
         const int o = c * kChunk8;
         *reinterpret_cast<float4*>(op + o) = make_float4(ov[0], ov[1], ov[2], ov[3]);
         *reinterpret_cast<float4*>(op + o + 4) = make_float4(ov[4], ov[5], ov[6], ov[7]);
@@ -291,6 +306,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1v2_kernel(
 #pragma unroll
         for (int i = 0; i < 8; ++i) if (i < rem) op[t0 + i] = Dval * cu[i] + cc[i] * (la[i] * hin + lb[i]);
         h = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ta), 63)) * h + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tb), 63));
+        if (xchunks) xc_record(xchunks, row, L, t0, kChunk8, lane, pr, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ta), 63)), h);
     }
     if (last_state && lane == 0) last_state[row] = h;
 }
@@ -433,10 +449,10 @@ constexpr int kScanV2MinLen = 4096;
 
 }  // namespace
 
-extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const float* A, const float* Bm,
-                                     const float* Cm, const float* Dv, const float* delta_bias, float* out,
-                                     float* last_state, int batch, int dim, int delta_dim, int seqlen, int dstate,
-                                     int ngroups, int delta_softplus, void* stream) {
+// x_chunks (batch, dim, ceil(seqlen / 2048), 2 dstate) or NULL: xp_selective_scan_fwd_x
+static int selective_scan_fwd_f32(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm, const float* Dv,
+                                  const float* delta_bias, float* out, float* last_state, float* x_chunks, int batch, int dim, int delta_dim,
+                                  int seqlen, int dstate, int ngroups, int delta_softplus, void* stream) {
     XP_CHECK_ARG(u && delta && A && Bm && Cm && out, "xp_selective_scan_fwd: null tensor pointer");
     XP_CHECK_ARG(batch > 0 && dim > 0 && seqlen > 0, "xp_selective_scan_fwd: batch/dim/seqlen must be positive");
     XP_CHECK_ARG(dstate > 0 && dstate <= 256, "xp_selective_scan_fwd: dstate must be in [1,256] (got %d)", dstate);
@@ -454,6 +470,7 @@ extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const f
     static const bool v1 = getenv("XP_SCAN_V1") != nullptr, v2 = getenv("XP_SCAN_V2") != nullptr;
     const bool use_v2 = v2 || (!v1 && seqlen >= kScanV2MinLen);
     static const bool old_gen = getenv("XP_SCAN_OLD_GEN") != nullptr;
+    XP_CHECK_ARG(!(x_chunks && old_gen && dstate > 1), "xp_selective_scan_fwd_x: XP_SCAN_OLD_GEN has no chunk-state output");
     // one profiling tag per kernel, so a test can tell which one ran
     const char* tag = dstate == 1 ? (!vec ? "selective_scan_fwd_n1s" : use_v2 ? "selective_scan_fwd_n1v2" : "selective_scan_fwd_n1")
                                   : (old_gen ? "selective_scan_fwd_old" : "selective_scan_fwd_gen");
@@ -461,17 +478,17 @@ extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const f
                      12.0 * batch * dim * (double)seqlen + 8.0 * batch * ngroups * dstate * (double)seqlen);
     if (dstate == 1) {
         if (vec && use_v2)
-            hipLaunchKernelGGL(selective_scan_fwd_n1v2_kernel, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state,
+            hipLaunchKernelGGL(selective_scan_fwd_n1v2_kernel, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, x_chunks,
                                batch, dim, delta_dim, seqlen, ngroups, delta_softplus);
         else if (vec)
-            hipLaunchKernelGGL(selective_scan_fwd_n1_kernel<true>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state,
+            hipLaunchKernelGGL(selective_scan_fwd_n1_kernel<true>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, x_chunks,
                                batch, dim, delta_dim, seqlen, ngroups, delta_softplus);
         else
-            hipLaunchKernelGGL(selective_scan_fwd_n1_kernel<false>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state,
+            hipLaunchKernelGGL(selective_scan_fwd_n1_kernel<false>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, x_chunks,
                                batch, dim, delta_dim, seqlen, ngroups, delta_softplus);
     } else {
         // d_state > 1: the 8-item DPP-scan kernel (the 4-item shuffle-scan kernel above ran at 0.08 of HBM at N = 16)
-        if (!old_gen) launch_gen<float, float, true>(u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, nullptr, batch, dim, delta_dim, seqlen, dstate, ngroups, delta_softplus, s);
+        if (!old_gen) launch_gen<float, float, true>(u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, x_chunks, batch, dim, delta_dim, seqlen, dstate, ngroups, delta_softplus, s);
         else if (vec)
             hipLaunchKernelGGL(selective_scan_fwd_kernel<true>, grid, block, 0, s, u, delta, A, Bm, Cm, Dv, delta_bias, out,
                                last_state, batch, dim, delta_dim, seqlen, dstate, ngroups, delta_softplus);
@@ -481,6 +498,22 @@ extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const f
     }
     XP_LAUNCH_CHECK();
     return XP_OK;
+}
+
+extern "C" int xp_selective_scan_fwd(const float* u, const float* delta, const float* A, const float* Bm,
+                                     const float* Cm, const float* Dv, const float* delta_bias, float* out,
+                                     float* last_state, int batch, int dim, int delta_dim, int seqlen, int dstate,
+                                     int ngroups, int delta_softplus, void* stream) {
+    return selective_scan_fwd_f32(u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, nullptr, batch, dim, delta_dim, seqlen, dstate, ngroups,
+                                  delta_softplus, stream);
+}
+
+extern "C" int xp_selective_scan_fwd_x(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm, const float* Dv,
+                                       const float* delta_bias, float* out, float* last_state, float* x_chunks, int batch, int dim, int delta_dim,
+                                       int seqlen, int dstate, int ngroups, int delta_softplus, void* stream) {
+    XP_CHECK_ARG(x_chunks, "xp_selective_scan_fwd_x: null x_chunks");
+    return selective_scan_fwd_f32(u, delta, A, Bm, Cm, Dv, delta_bias, out, last_state, x_chunks, batch, dim, delta_dim, seqlen, dstate, ngroups,
+                                  delta_softplus, stream);
 }
 
 // itype: 0 f32, 1 f16, 2 bf16 (u, delta, B, C); out_float != 0: out is f32 ("oflex"), else out has the input type.
