@@ -541,6 +541,39 @@ int xp_ha_accumulate(const float* prob, const float* M, const uint8_t* mask, flo
                      int first_direct, int H, int W, int mode, int window_size, int weighted, int finalize, float min_count, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training losses.  Replace the eager XPointLoss.descriptor_loss (dense form) and XPointLoss.detector_loss
+ * (xpoint/utils/losses.py:688-755, 374-576); Python caller xpoint_amd/losses.py.
+ *
+ * Dense descriptor loss.  d1, d2 (B, D, Hc, Wc) f32 (NCHW), D % 16 == 0, 16 <= D <= 256; w1, w2 (B, Hc*Wc, 2) f32 = the cell centres
+ * (8y+4, 8x+4) carried into the common frame, (y, x) order, or NULL (the centres themselves); v1, v2 (B, Hc*Wc) f32 cell masks or NULL
+ * (ones).  With j a cell of image 2 and i a cell of image 1: s = [|w1_i - w2_j| <= threshold], dot = <d2_j, d1_i>, v = v2_j v1_i,
+ *   pos = lambda_d s max(0, positive_margin - dot) v,  neg = (1 - s) max(0, dot - negative_margin) v.
+ * xp_descriptor_loss_fwd writes sums (B, 3) = sum_ji of (pos + neg, pos, neg) and norm (B) = sum v2 * sum v1 (no clamp), and leaves the
+ * staged split-fp16 operand planes, cell data and scales in the workspace; xp_descriptor_loss_bwd takes THAT workspace unchanged (same
+ * shapes and parameters) and coef (B) device f32 = dL / d(sums[b, 0]) and writes dD1 / dD2 (B, D, Hc, Wc) (either may be NULL).
+ * dot is evaluated as three fp16 products of split operands with f32 accumulation (f32-grade); inputs are scaled by one power of two per
+ * sample, so any finite range is accepted.  The workspace is linear in Hc*Wc (no (HW, HW) tensor is ever written); sums run in a fixed
+ * order without atomics: two calls are bit-identical and sample b's results do not depend on the other samples.  256-byte aligned workspace. */
+size_t xp_descriptor_loss_workspace_bytes(int B, int D, int Hc, int Wc);
+int xp_descriptor_loss_fwd(const float* d1, const float* d2, const float* w1, const float* w2, const float* v1, const float* v2, int B, int D,
+                           int Hc, int Wc, float threshold, float positive_margin, float negative_margin, float lambda_d, void* workspace,
+                           size_t workspace_bytes, float* sums, float* norm, void* stream);
+int xp_descriptor_loss_bwd(const float* coef, int B, int D, int Hc, int Wc, float threshold, float positive_margin, float negative_margin,
+                           float lambda_d, const void* workspace, size_t workspace_bytes, float* dD1, float* dD2, void* stream);
+
+/* Detector loss with 'hard_assignment'.  logits (B, 65, Hc, Wc) f32; keypoint_map (B, 8Hc, 8Wc) f32; valid_mask (B, 8Hc, 8Wc) f32 or NULL;
+ * noise (B, 64, Hc, Wc) f32 = the reference's torch.rand(labels.shape).  kind 0: cross entropy with class weights [1]*64 + [dustbin_weight];
+ * kind 1: focal loss alpha (1 - pt)^gamma ce.  Outputs, all (B, Hc*Wc) unless stated: labels int32 (argmax over [3 label + noise, 2.0], first
+ * maximum), valid f32 (block product of the mask), cell_loss f32 (loss * valid), cell_code int32 (bit 0 correct, 1 TP, 2 FP, 3 FN, 4 TN: the
+ * statistics compare argmax softmax(logits) with label * valid), stats (B, 8) f64 = [sum cell_loss, sum valid, correct, TP, FP, FN, TN, 0],
+ * summed in a fixed order.  xp_detector_loss_bwd: coef (B) device f32 = dL / d(stats[b, 0]); writes dlogits (B, 65, Hc, Wc). */
+int xp_detector_loss_fwd(const float* logits, const float* keypoint_map, const float* valid_mask, const float* noise, int B, int Hc, int Wc,
+                         int kind, float dustbin_weight, float alpha, float gamma, int* labels, float* valid, float* cell_loss, int* cell_code,
+                         double* stats, void* stream);
+int xp_detector_loss_bwd(const float* logits, const int* labels, const float* valid, const float* coef, int B, int Hc, int Wc, int kind,
+                         float dustbin_weight, float alpha, float gamma, float* dlogits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -110,6 +110,10 @@ _SIGNATURES = {
     "xp_ha_valid_mask": [c_p] * 3 + [c_i] * 5 + [c_p],
     "xp_ha_gaussian": [c_p] * 3 + [c_i] * 4 + [c_p],
     "xp_ha_accumulate": [c_p] * 6 + [c_i] * 9 + [c_f, c_p],
+    "xp_descriptor_loss_fwd": [c_p] * 6 + [c_i] * 4 + [c_f] * 4 + [c_p, c_sz, c_p, c_p, c_p],
+    "xp_descriptor_loss_bwd": [c_p] + [c_i] * 4 + [c_f] * 4 + [c_p, c_sz, c_p, c_p, c_p],
+    "xp_detector_loss_fwd": [c_p] * 4 + [c_i] * 4 + [c_f] * 3 + [c_p] * 6,
+    "xp_detector_loss_bwd": [c_p] * 4 + [c_i] * 4 + [c_f] * 3 + [c_p] * 2,
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -125,6 +129,7 @@ _SIZE_QUERIES = {
     "xp_forward_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
     "xp_ss2d_core_workspace_bytes": (c_sz, [c_i] * 4),
     "xp_selective_scan_bwd_workspace_bytes": (c_sz, [c_i] * 6),
+    "xp_descriptor_loss_workspace_bytes": (c_sz, [c_i] * 4),
     "xp_split_weights_x3_bytes": (c_sz, [c_i] * 2),
     "xp_split_weights_h2_bytes": (c_sz, [c_i] * 2),
     "xp_p32_bytes": (c_sz, [c_l, c_i]),
