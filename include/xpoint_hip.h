@@ -469,6 +469,44 @@ int xp_match_cand_cap(void);
 int xp_points_min_dist(const double* a, int na, const float* b, int nb, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Detector evaluation against keypoint labels: the true / false positive assignment and the prediction-label distances of
+ * xpoint/utils/evaluation.py:57-97 (compute_tp_fp_dist) for a batch of heat maps, without the (predictions x labels)
+ * distance matrix and without a sequential walk over the predictions.  Four launches; the sort that ranks the candidates and the
+ * scan of the pair counts between them are the caller's (xpoint_amd/evaluation.py uses torch on the device).  Every quantity is
+ * per image: image b of a batch gets the bits it gets alone.
+ *   prob (batch, H, W) f32, labels (batch, H, W) u8 (non-zero = label).  A candidate is a pixel with prob > zero_threshold
+ *   (zero_threshold >= 0, so candidates are positive).  Rank order: descending prob, ties by ascending row-major pixel index
+ *   (this project's rule; the reference leaves equal probabilities to torch.sort).  Rank key (u64, formed in registers): high word
+ *   = ~(float bits of prob), low word = pixel index — a smaller key ranks first.  The same order over an image is a STABLE
+ *   descending sort of cand_prob, which is how the caller obtains rank_pix.
+ *   distance_thresh in [0, 8]; H * W must fit 32 bits; batch <= 65535.  A label is "within the radius" of a pixel when
+ *   sqrtf(dy*dy + dx*dx) <= distance_thresh in f32 (torch.norm of the integer difference cast to float).
+ *
+ * xp_detector_eval_claim   per candidate: scans the (2 floor(distance_thresh) + 1)^2 window of the label map in row-major order;
+ *                          first_label = pixel index of the first label within the radius (0xFFFFFFFF: none), n_within = their
+ *                          number, and atomicMin(winner[first_label], key).  cand_prob = prob at a candidate, 0 elsewhere.
+ *                          cand_prob / winner / first_label / n_within are (batch, H*W); winner is initialised here (all ones).
+ *                          n_cand / n_gt (batch) int32: candidates and labels per image.
+ * xp_detector_eval_resolve tp_pix (batch, H*W) u8 = the pixel is a candidate, has a first label and its key is that label's
+ *                          winner — i.e. it is the best-ranked prediction claiming the label, which is what the reference's loop
+ *                          computes (incl. "no label left": a label that is taken stays taken; zero labels: nothing matches).
+ * xp_detector_eval_gather  rank_pix (batch, H*W) i64: the pixel index of every rank (ranks >= n_cand[b] are ignored).  Per rank:
+ *                          tp_sorted = tp_pix of its pixel, cnt_sorted = n_within of its pixel; 0 past the candidates.
+ * xp_detector_eval_fill_dist  dist[incl[b, i] - cnt_sorted[b, i] + k] = distance to the k-th (row-major) label within the radius
+ *                          of rank i's pixel; incl = inclusive scan (i64) of cnt_sorted over the flattened (batch, H*W) array, so
+ *                          dist (dist_len f32) is the reference's dist[matches] of image 0, then image 1, ...  Writes outside
+ *                          [0, dist_len) are dropped. */
+int xp_detector_eval_claim(const float* prob, const uint8_t* labels, int batch, int H, int W, float zero_threshold, float distance_thresh,
+                           float* cand_prob, unsigned long long* winner, unsigned int* first_label, int* n_within,
+                           int* n_cand, int* n_gt, void* stream);
+int xp_detector_eval_resolve(const float* cand_prob, const unsigned long long* winner, const unsigned int* first_label, int batch,
+                             int H, int W, uint8_t* tp_pix, void* stream);
+int xp_detector_eval_gather(const long long* rank_pix, const uint8_t* tp_pix, const int* n_within, const int* n_cand, int batch, int H, int W,
+                            uint8_t* tp_sorted, int* cnt_sorted, void* stream);
+int xp_detector_eval_fill_dist(const long long* rank_pix, const uint8_t* labels, const long long* incl, const int* cnt_sorted,
+                               int batch, int H, int W, float distance_thresh, float* dist, long long dist_len, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Robust homography from point correspondences, batched over pairs: the device-side stand-in
  * for cv2.findHomography(src, dst, cv2.USAC_MAGSAC, ransacReprojThreshold, confidence, maxIters) as called from
  * predict_align_image_pair.py:291-303 and benchmark_evaluation.py:796-812.  Same contract (H maps src -> dst, h33 = 1;

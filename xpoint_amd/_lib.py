@@ -102,6 +102,10 @@ _SIGNATURES = {
     "xp_match_threshold": [c_p, c_p, c_p] + [c_i] * 7 + [ctypes.c_double, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_sz, c_p],
     "xp_match_stats": [c_p, c_p] + [c_i] * 7 + [c_p, c_p],
     "xp_points_min_dist": [c_p, c_i, c_p, c_i, c_p, c_p],
+    "xp_detector_eval_claim": [c_p, c_p, c_i, c_i, c_i, c_f, c_f] + [c_p] * 7,
+    "xp_detector_eval_resolve": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
+    "xp_detector_eval_gather": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    "xp_detector_eval_fill_dist": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_l, c_p],
     "xp_gather_match_points": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "xp_find_homography": [c_p, c_p, c_p, c_i, c_i, c_f, c_i, ctypes.c_uint, c_p, c_p, c_p, c_p, c_sz, c_p],
     "xp_warp_perspective": [c_p, c_p, c_p] + [c_i] * 9 + [c_p],

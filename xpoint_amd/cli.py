@@ -2,15 +2,20 @@
 (predict_align_image_pair.py:24-37, predict_keypoints.py: the same -y / -m / -v / -i / -s options):
 
     python -m xpoint_amd.cli align     -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e] [-o out.npz]
-    python -m xpoint_amd.cli keypoints -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-o out.npz]
+    python -m xpoint_amd.cli keypoints -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e [-t 3]] [-o out.npz]
     python -m xpoint_amd.cli export    -y configs/config_export_keypoints.yaml -m model_weights/XPoint-EXP1 -v latest -o labels.npz
                                        [-i 0] [-n all] [-s 0] [--chunk K]
 
 What is kept from the scripts: the YAML handling (model params from <model-dir>/params.yaml overwrite config['model'], the
 `use_attention` height / width patch of predict_align_image_pair.py:50-54), `<model-dir>/<version>.model` loaded with
 `strict=False` after `fix_model_weigth_keys`, the seeds, the per-sample flow.  What is not: plotting (-p, -r) and the HDF5
-datasets — the dataset must be a folder dataset (`dataset.foldername`, xpoint_amd/datasets.py).  `-e` adds the registration
+datasets — the dataset must be a folder dataset (`dataset.foldername`, xpoint_amd/datasets.py).  `align -e` adds the registration
 step (robust homography per pair) and prints the inlier counts.  Prints one line per sample and a timing summary.
+
+`keypoints -e [-t 3]` is the evaluation half of predict_keypoints.py:88-142 (see `evaluate_keypoints`): the repeatability of the detector
+over the WHOLE dataset in batches of prediction.batchsize, printed in the script's three lines and, with -o, stored as repeatability_mean,
+repeatability, n_kp_optical, n_kp_thermal and distance_threshold next to the per-sample keypoints.  When the dataset carries keypoint labels
+(dataset.keypoints_filename: an .npz as `export` writes it) it additionally reports mAP and the mean prediction-label distance per spectrum.
 
 `export` is export_keypoints.py: label export by homographic adaptation (xpoint_amd.homographies, config key
 prediction.homographic_adaptation) with the model params of <model-dir>/params.yaml, takes_pair and the homography head off, seeds as
@@ -45,11 +50,16 @@ def load_config(yaml_config: str, model_dir: str) -> dict:
 
 
 def build(config: dict, model_dir: str, version: str, device: str):
-    from . import datasets, models, utils
+    from . import datasets
     ds_cfg = dict(config['dataset'])
     ds_cfg.pop('type', None)
     ds_cfg['single_image'] = False
     dataset = datasets.ImagePairDataset(ds_cfg)
+    return dataset, build_net(config, model_dir, version, device)
+
+
+def build_net(config: dict, model_dir: str, version: str, device: str):
+    from . import models, utils
     net = getattr(models, config['model']['type'])(config['model'])
     if version != 'none':
         weights = torch.load(os.path.join(model_dir, version + '.model'), map_location=torch.device('cpu'))
@@ -61,7 +71,56 @@ def build(config: dict, model_dir: str, version: str, device: str):
             raise ValueError("No weights were loaded correctly! Please check the model and weights file.")
     net.to(device)
     net.eval()
-    return dataset, net
+    return net
+
+
+def evaluate_keypoints(args, config, dataset, net) -> dict:
+    """predict_keypoints.py:88-142 for a pair dataset: seeds as the script, compute_repeatability_multispectral over the whole dataset in
+    batches of prediction.batchsize, the script's three printed lines; returns repeatability_mean, repeatability, n_kp_optical,
+    n_kp_thermal, distance_threshold.
+
+    Extension: when the dataset carries keypoint labels, compute_detector_metrics runs once per spectrum on the same crops (the seeds are set
+    again before every pass) and detector_<spectrum>_{precision, recall, prob, dist, mAP, mean_dist} are added.  The reference offers these
+    numbers only for single-image HDF5 datasets (its `else` branch); here they come from the pair dataset's per-spectrum labels, through a
+    single-image forward — the model built with takes_pair and the homography head off, as `export` builds it."""
+    import copy
+    from . import evaluation
+    pred = config['prediction']
+    bs = int(pred.get('batchsize', 1))
+
+    def seed():
+        random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
+
+    def loader(spec=None):
+        for i0 in range(0, len(dataset), bs):
+            batch = dataset.load_batch(list(range(i0, min(i0 + bs, len(dataset)))), args.device)
+            yield batch if spec is None else dict(batch[spec])
+
+    seed()
+    mean, rep, n_o, n_t = evaluation.compute_repeatability_multispectral(net, loader(), args.device, config, distance_thresh=args.threshold)
+    print('Repeatability: {}'.format(mean))
+    print('Number of optical keypoints: {}'.format(np.mean(n_o)))
+    print('Number of thermal keypoints: {}'.format(np.mean(n_t)))
+    res = {'repeatability_mean': mean, 'repeatability': np.asarray(rep, np.float64), 'n_kp_optical': np.asarray(n_o, np.int64),
+           'n_kp_thermal': np.asarray(n_t, np.int64), 'distance_threshold': args.threshold}
+    if dataset.config['keypoints_filename'] is not None:
+        net1 = net
+        if net.takes_pair():
+            cfg1 = copy.deepcopy(config)
+            cfg1['model']['takes_pair'] = False
+            if 'homography_regression_head' in cfg1['model']:
+                cfg1['model']['homography_regression_head']['check'] = False
+            net1 = build_net(cfg1, args.model_dir, args.version, args.device)
+        for spec in ('optical', 'thermal'):
+            seed()
+            precision, recall, prob, dist = evaluation.compute_detector_metrics(net1, loader(spec), args.device, pred)
+            m_ap = float(evaluation.compute_mAP(precision, recall))
+            mean_dist = float(dist.mean()) if len(dist) else float('nan')
+            print('{}: mAP: {}'.format(spec, m_ap))
+            print('{}: Average distance of the predictions to the labels within the radius: {}'.format(spec, mean_dist))
+            res.update({f'detector_{spec}_precision': precision, f'detector_{spec}_recall': recall, f'detector_{spec}_prob': prob,
+                        f'detector_{spec}_dist': dist, f'detector_{spec}_mAP': m_ap, f'detector_{spec}_mean_dist': mean_dist})
+    return res
 
 
 def main(argv=None):
@@ -72,7 +131,10 @@ def main(argv=None):
     ap.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
     ap.add_argument('-i', '--index', default=0, type=int, help='Index of the first sample')
     ap.add_argument('-n', '--count', default=None, type=int, help='Number of consecutive samples (default 1; export: all)')
-    ap.add_argument('-e', dest='evaluation', action='store_true', help='align: also estimate the homography of every pair and warp the optical image with it')
+    ap.add_argument('-e', dest='evaluation', action='store_true',
+                    help='align: also estimate the homography of every pair and warp the optical image with it; keypoints: compute the repeatability '
+                         'over the whole dataset (and, if the dataset has keypoint labels, mAP and the mean label distance per spectrum)')
+    ap.add_argument('-t', dest='threshold', default=3, type=int, help='keypoints -e: distance threshold for two keypoints to be considered a match')
     ap.add_argument('--save-warped', default=None, metavar='DIR', help='align -e: write the warped optical image of every sample to DIR/<name>_warped.png')
     ap.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
     ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz')
@@ -95,6 +157,8 @@ def main(argv=None):
     out = {}
     t_total = 0.0
     with torch.no_grad():
+        if args.flow == 'keypoints' and args.evaluation:
+            out.update(evaluate_keypoints(args, config, dataset, net))
         for idx in range(args.index, min(args.index + args.count, len(dataset))):
             data = dataset.load_batch([idx], args.device)
             torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -6,7 +6,11 @@ What is mirrored: the config keys `foldername`, `height`, `width`, `single_image
 the folder check (`optical/` + `thermal/` or `images/`), the same-shape check, the random crop (same `random.randint`
 call order: i_h, then i_w) and the output structure `{'optical': {'image' (1,h,w) f32, 'valid_mask' (1,h,w) bool,
 'is_optical'}, 'thermal': {...}, 'name'}` that `XPoint.forward` / `predict_align_image_pair` consume.
-Not mirrored (training side, SURVEY.md 2 "out of scope"): the HDF5 file mode, keypoint label files, photometric /
+Keypoint labels: `keypoints_filename` accepts an .npz in the layout `python -m xpoint_amd.cli export` writes (`<name>/keypoints`, or
+`<name>/keypoints_optical` + `<name>/keypoints_thermal`; <name> = the image file name) in place of the reference's HDF5 file (:133-169 the
+"labels for every sample" check, :223-231 the read, :276-294 shift by the crop origin and drop what falls outside, :407-427
+`generate_keypoint_map`): `['optical']['keypoints']` and `['thermal']['keypoints']` are (h, w) bool maps.
+Not mirrored (training side, SURVEY.md 2 "out of scope"): the HDF5 file mode, HDF5 label files, photometric /
 homographic augmentation — a config that asks for them raises.
 
 Decode: PIL (the image has no OpenCV).  Gray conversion and normalisation follow OpenCV's 8-bit `COLOR_BGR2GRAY`
@@ -70,8 +74,10 @@ class ImagePairDataset:
             raise NotImplementedError("ImagePairDataset: only the folder mode is implemented (h5py is not available here)")
         if self.config['foldername'] is None:
             raise ValueError("ImagePairDataset: The dataset filename XOR foldername needs to be present in the config file")
-        if self.config['keypoints_filename'] is not None:
-            raise NotImplementedError("ImagePairDataset: keypoint label files belong to the training path (out of scope)")
+        self._labels = None
+        if self.config['keypoints_filename'] is not None and not str(self.config['keypoints_filename']).endswith(".npz"):
+            raise NotImplementedError("ImagePairDataset: keypoint label files are read from an .npz in the layout `cli export` writes; "
+                                      "HDF5 label files need h5py, which is not available here")
         aug = self.config['augmentation']
         if aug['photometric'].get('enable') or aug['homographic'].get('enable'):
             raise NotImplementedError("ImagePairDataset: augmentation belongs to the training path (out of scope)")
@@ -84,9 +90,37 @@ class ImagePairDataset:
         self.memberslist = sorted(f for f in os.listdir(self.data_path[0]) if f.endswith(".jpg") or f.endswith(".png"))
         self.num_files = len(self.memberslist)
         self._lut_dev = {}
+        if self.config['keypoints_filename'] is not None:
+            with np.load(self.config['keypoints_filename']) as f:
+                self._labels = {k: np.asarray(f[k]).astype(np.int64).reshape(-1, 2) for k in f.files}
+            missing = [m for m in self.memberslist if self._label_keys(m) is None]          # reference :146-169
+            if missing:
+                raise IndexError("Labels for the following samples (display only first 10) not available: {}, len : {}".format(
+                    missing[:10], len(missing)))
 
     def __len__(self):
         return self.num_files
+
+    # ---- keypoint labels -------------------------------------------------------------------------------------
+    def _label_keys(self, name):
+        """(optical key, thermal key) of a member in the label file, or None: one list for both spectra, or one per spectrum."""
+        if f"{name}/keypoints_optical" in self._labels and f"{name}/keypoints_thermal" in self._labels:
+            return f"{name}/keypoints_optical", f"{name}/keypoints_thermal"
+        if f"{name}/keypoints" in self._labels:
+            return f"{name}/keypoints", f"{name}/keypoints"
+        return None
+
+    def _label_maps(self, index, i_h, i_w, h, w):
+        """Reference :276-294 + :407-427: the (h, w) bool label maps of the optical and the thermal slot (the labels stay with their slot
+        under random_pairs, as in the reference).  With a crop the points move by its origin and those outside are dropped."""
+        maps = []
+        for key in self._label_keys(self.memberslist[index]):
+            kp = self._labels[key]
+            if self.config['height'] > 0 or self.config['width'] > 0:
+                kp = kp - np.array([[i_h, i_w]])
+                kp = kp[np.logical_and(np.logical_and(kp[:, 0] >= 0, kp[:, 0] < h), np.logical_and(kp[:, 1] >= 0, kp[:, 1] < w))]
+            maps.append(utils.generate_keypoint_map(kp, (h, w)))
+        return maps
 
     # ---- host side -------------------------------------------------------------------------------------------
     def _decode(self, index):
@@ -141,6 +175,8 @@ class ImagePairDataset:
             out[key]['image'] = torch.from_numpy(np.expand_dims(img, 0).astype(np.float32))
             out[key]['valid_mask'] = torch.ones((1, h, w), dtype=torch.bool)
             out[key]['is_optical'] = torch.BoolTensor([flag])
+        if self._labels is not None:
+            out['optical']['keypoints'], out['thermal']['keypoints'] = (torch.from_numpy(m) for m in self._label_maps(index, i_h, i_w, h, w))
         if self.config['return_name']:
             out['name'] = self.memberslist[index]
         return out
@@ -159,6 +195,7 @@ class ImagePairDataset:
         imgs = {'optical': None, 'thermal': None}
         flags = {'optical': [], 'thermal': []}
         names = []
+        labels = {'optical': [], 'thermal': []}
         st = L.current_stream(device)
         keep = []
         for bi, index in enumerate(indices):
@@ -180,11 +217,16 @@ class ImagePairDataset:
                        ctypes.c_void_p(imgs[key][bi].data_ptr()), st)
             flags['optical'].append([o_flag]); flags['thermal'].append([t_flag])
             names.append(self.memberslist[index])
+            if self._labels is not None:
+                mo, mt = self._label_maps(index, i_h, i_w, h, w)
+                labels['optical'].append(mo); labels['thermal'].append(mt)
         torch.cuda.current_stream(device).synchronize()      # the staging buffers in `keep` may go now
         out = {}
         for key in ('optical', 'thermal'):
             out[key] = {'image': imgs[key], 'valid_mask': torch.ones_like(imgs[key], dtype=torch.bool),
                         'is_optical': torch.tensor(flags[key], dtype=torch.bool, device=device)}
+            if self._labels is not None:
+                out[key]['keypoints'] = torch.from_numpy(np.stack(labels[key])).to(device)
         if self.config['return_name']:
             out['name'] = names
         return out

@@ -13,6 +13,12 @@ structures, including its per-sample overwrite quirks, see below) and `xpoint/ut
                                                                         same contract, not bit-comparable — §8(f) rank 2)
   compute_metrics                    benchmark_evaluation.py:832-963
 
+and the detector half of `xpoint/utils/evaluation.py` (what `predict_keypoints.py -e` runs):
+
+  compute_tp_fp_dist                 evaluation.py:57-97    (tp / fp against keypoint labels; tp_fp_dist_batched is the device form)
+  compute_detector_metrics           evaluation.py:10-55    (precision / recall over a data set)
+  compute_repeatability_multispectral evaluation.py:105-204
+
 Device work goes through the C ABI: keypoints and descriptors stay on the GPU, descriptor sampling is
 `xp_sample_descriptors`, both match directions come from ONE `xp_match_mnn` call (mutual nearest neighbours are
 the same pairs seen from either side), and the N x M "distance to the nearest keypoint" matrices of the reference
@@ -327,6 +333,200 @@ def compute_metrics(net, dataloader, device, config, keypoint_detection_threshol
     tw = thresh_warp if type(thresh_warp) is list else [thresh_warp]
     return {"repeatability": out_rep, "descriptor": compute_desc_dict(descriptor_metrics_dict),
             "homography": compute_homography_dict(overall_pts_dist_dict, tw)}
+
+
+# ------------------------------------------------------------------------------------------------
+# Detector evaluation against keypoint labels: reference xpoint/utils/evaluation.py (compute_tp_fp_dist, compute_detector_metrics,
+# compute_repeatability_multispectral) — the evaluation half of predict_keypoints.py -e.
+# ------------------------------------------------------------------------------------------------
+def _div0_one(a, b):
+    """The div0 of reference evaluation.py:206-211 (and utils.py:127-132): a / b, and where that is not finite 1 if a == 0 else 0 — so a
+    data set without labels has recall 1, unlike `div0` above (benchmark_evaluation.py's, 0 there)."""
+    a = np.asarray(a)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        c = np.true_divide(a, b)
+        idx = ~np.isfinite(c)
+        c[idx] = np.where(a[idx] == 0, 1, 0)
+    return c
+
+
+def tp_fp_dist_batched(prob, keypoints, zero_threshold=1e-4, distance_thresh=2.0):
+    """compute_tp_fp_dist (evaluation.py:57-97) for a batch on the device: prob (B, H, W) float32, keypoints (B, H, W) label maps (bool /
+    uint8 / anything whose non-zeros are labels), both on the GPU.  Returns one (tp bool[P], fp bool[P], prob float32[P] descending,
+    n_gt int, dist float32[M]) per image, as device tensors (views of batch-wide buffers).
+
+    Formulation (include/xpoint_hip.h, xp_detector_eval_*; DESIGN.md "Detector evaluation"): a candidate is a pixel with prob >
+    zero_threshold; each claims the first row-major label within the radius with a u64 atomic minimum of its rank key, and is a true
+    positive iff it holds its label's minimum — the reference's greedy loop, with no (predictions x labels) tensor and no loop over
+    either.  Rank order: descending prob, equal probabilities by ascending row-major pixel index (this project's rule: the reference's
+    order among exact ties is whatever torch.sort does).  dist holds every within-radius (prediction, label) pair, not only the true
+    positives, ordered by (rank, row-major label) — the reference's dist[matches].
+    Device plumbing between the four launches: one stable torch.sort of the candidate probabilities per image (a loop over the images
+    of the batch) and one cumsum of the pair counts.  One
+    synchronisation: the per-image counts come back in a single copy, which sizes `dist`.  Every output of image b is what the image
+    gives alone."""
+    if not (torch.is_tensor(prob) and prob.is_cuda and prob.dim() == 3):
+        raise ValueError("tp_fp_dist_batched: prob must be a (B, H, W) tensor on the GPU (no CPU fallback)")
+    if not (torch.is_tensor(keypoints) and keypoints.is_cuda and tuple(keypoints.shape) == tuple(prob.shape)):
+        raise ValueError("tp_fp_dist_batched: keypoints must be a (B, H, W) label map on the device of prob")
+    B, H, W = (int(v) for v in prob.shape)
+    if B == 0:
+        return []
+    p = prob.contiguous().float()
+    kp = keypoints.contiguous()
+    lab = kp.view(torch.uint8) if kp.dtype == torch.bool else (kp if kp.dtype == torch.uint8 else (kp != 0).view(torch.uint8))
+    HW = H * W
+    dev = p.device
+    v = ctypes.c_void_p
+    with torch.cuda.device(dev):
+        st = _lib.current_stream(dev)
+        cand = torch.empty((B, HW), dtype=torch.float32, device=dev)
+        winner = torch.empty((B, HW), dtype=torch.int64, device=dev)
+        first = torch.empty((B, HW), dtype=torch.int32, device=dev)
+        within = torch.empty((B, HW), dtype=torch.int32, device=dev)
+        counts = torch.empty((2, B), dtype=torch.int32, device=dev)
+        _lib.call("xp_detector_eval_claim", v(p.data_ptr()), v(lab.data_ptr()), B, H, W, float(zero_threshold), float(distance_thresh),
+                  v(cand.data_ptr()), v(winner.data_ptr()), v(first.data_ptr()), v(within.data_ptr()), v(counts[0].data_ptr()),
+                  v(counts[1].data_ptr()), st)
+        tp_pix = torch.empty((B, HW), dtype=torch.uint8, device=dev)
+        _lib.call("xp_detector_eval_resolve", v(cand.data_ptr()), v(winner.data_ptr()), v(first.data_ptr()), B, H, W, v(tp_pix.data_ptr()), st)
+        del winner, first
+        # the rank order = the order of the u64 keys: descending probability, equal ones by ascending pixel index (the sort is stable and
+        # its input is in pixel order); non-candidates are 0 in `cand` and come last.  One image at a time: a 1-D sort's temporaries
+        # are those of one image, and they are gone before the next.
+        prob_s = torch.empty((B, HW), dtype=torch.float32, device=dev)
+        rank_pix = torch.empty((B, HW), dtype=torch.int64, device=dev)
+        for b in range(B):
+            torch.sort(cand[b], descending=True, stable=True, out=(prob_s[b], rank_pix[b]))
+        del cand
+        tp_s = torch.empty((B, HW), dtype=torch.bool, device=dev)
+        cnt_s = torch.empty((B, HW), dtype=torch.int32, device=dev)
+        _lib.call("xp_detector_eval_gather", v(rank_pix.data_ptr()), v(tp_pix.data_ptr()), v(within.data_ptr()), v(counts[0].data_ptr()), B, H, W,
+                  v(tp_s.data_ptr()), v(cnt_s.data_ptr()), st)
+        del tp_pix, within
+        incl = torch.cumsum(cnt_s.view(-1), 0, dtype=torch.int64)
+        host = torch.cat([counts.view(-1).to(torch.int64), incl.view(B, HW)[:, -1]]).cpu().tolist()         # the one synchronisation
+        n_cand, n_gt, ends = host[:B], host[B:2 * B], [0] + host[2 * B:]
+        dist = torch.empty((ends[-1],), dtype=torch.float32, device=dev)
+        _lib.call("xp_detector_eval_fill_dist", v(rank_pix.data_ptr()), v(lab.data_ptr()), v(incl.data_ptr()), v(cnt_s.data_ptr()), B, H, W,
+                  float(distance_thresh), v(dist.data_ptr()) if ends[-1] else None, ends[-1], st)
+    out = []
+    for b in range(B):
+        tp = tp_s[b, :n_cand[b]]
+        out.append((tp, ~tp, prob_s[b, :n_cand[b]], n_gt[b], dist[ends[b]:ends[b + 1]]))
+    return out
+
+
+def _as_device_tensor(x, device, dtype=None):
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(device=device, dtype=dtype) if dtype is not None else t.to(device)
+
+
+def compute_tp_fp_dist(prob, keypoints, zero_threshold=1e-4, distance_thresh=2.0):
+    """evaluation.py:57-97, same returns: (tp bool[P], fp bool[P], prob float32[P] descending, n_gt int, dist float32[M]) as numpy.
+    prob (H, W): tensor (any device) or array; keypoints: a label map of the same shape, or — any other shape — a point list (N, 2) of
+    (y, x), turned into a map by utils.generate_keypoint_map as in the reference.  Runs on the GPU (tp_fp_dist_batched with B = 1; the
+    device of prob if it has one, else the current one); equal probabilities rank by ascending pixel index."""
+    if not torch.cuda.is_available():
+        raise _lib.XPointHipError("xpoint_amd.evaluation.compute_tp_fp_dist runs on the GPU only (no CPU fallback)")
+    device = prob.device if torch.is_tensor(prob) and prob.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if tuple(prob.shape) != tuple(keypoints.shape):
+        pts = keypoints.cpu().numpy() if torch.is_tensor(keypoints) else np.asarray(keypoints)
+        keypoints = utils.generate_keypoint_map(pts, tuple(prob.shape))
+    p = _as_device_tensor(prob, device, torch.float32)
+    k = _as_device_tensor(keypoints, device)
+    tp, fp, pr, n_gt, dist = tp_fp_dist_batched(p[None], k[None], zero_threshold, distance_thresh)[0]
+    return tp.cpu().numpy(), fp.cpu().numpy(), pr.cpu().numpy(), n_gt, dist.cpu().numpy()
+
+
+def compute_detector_metrics(net, dataloader, device, config):
+    """evaluation.py:10-55: precision / recall of a single-image detector against the keypoint labels of a data set.  `dataloader`:
+    any iterable of single-image data dicts {'image' (B,1,H,W), 'valid_mask', 'keypoints' (B,H,W) label maps, ...}; `net(data)` returns
+    {'prob' (B,1,H,W)}; config: the prediction section ('nms', 'detection_threshold').  Returns (precision, recall, prob, dist).
+    Per batch: out['prob'] * valid_mask, box_nms(pred, nms, detection_threshold) when nms > 0 (no keep_top_k, as the reference), then
+    ONE tp_fp_dist_batched call.  Across images the results are concatenated in order and sorted by descending prob with ties in
+    concatenation order (the reference: np.argsort(prob)[::-1], unspecified among ties); prob and dist come back as float64 (the reference
+    goes through .tolist()).  Cumulative sums and the precision envelope are host numpy, like the rest of this module."""
+    tp, prob, dist, n_gt = [], [], [], 0
+    for data in dataloader:
+        data = utils.data_to_device(data, device)
+        out = net(data)
+        pred = out['prob'] * data['valid_mask']
+        if config['nms'] > 0:
+            pred = utils.box_nms(pred, config['nms'], config['detection_threshold'])
+        res = tp_fp_dist_batched(pred[:, 0], data['keypoints'].reshape(pred[:, 0].shape))
+        n = [len(r[0]) for r in res]
+        m = [len(r[4]) for r in res]
+        # three copies for the whole batch (the per-image results are views of batch-wide buffers, in image order)
+        tp.append(torch.cat([r[0] for r in res]).cpu().numpy()); prob.append(torch.cat([r[2] for r in res]).cpu().numpy().astype(np.float64))
+        dist.append(torch.cat([r[4] for r in res]).cpu().numpy().astype(np.float64))
+        n_gt += sum(r[3] for r in res)
+        assert len(tp[-1]) == sum(n) and len(dist[-1]) == sum(m)
+    tp = np.concatenate(tp) if tp else np.zeros((0,), bool)
+    prob = np.concatenate(prob) if prob else np.zeros((0,), np.float64)
+    dist = np.concatenate(dist) if dist else np.zeros((0,), np.float64)
+    fp = np.logical_not(tp)
+    sort_idx = np.argsort(-prob, kind="stable")
+    tp, fp, prob = tp[sort_idx], fp[sort_idx], prob[sort_idx]
+    tp_cum, fp_cum = np.cumsum(tp), np.cumsum(fp)
+    recall = _div0_one(tp_cum, n_gt)
+    precision = _div0_one(tp_cum, tp_cum + fp_cum)
+    recall = np.concatenate([[0], recall, [1]])
+    precision = np.concatenate([[0], precision, [0]])
+    precision = np.maximum.accumulate(precision[::-1])[::-1]
+    return precision, recall, prob, dist
+
+
+def compute_repeatability_multispectral(net, dataloader, device, config, distance_thresh=3, verbose=False):
+    """evaluation.py:105-204: (mean repeatability, list per sample, n_kp_optical list, n_kp_thermal list).  Reads config['prediction']
+    (detection_threshold, nms, topk, cpu_nms); homographies default to identity; keypoints = nonzero((prob > thr) * valid_mask) of the
+    (optionally box_nms'ed, UNMASKED) heat map; each set is warped into the other frame with the truncating warp_keypoints through
+    H.inverse() (float32, torch) and then the other H, and filtered to the image; the "distance to the nearest keypoint" of the reference's
+    all-pairs norm goes through xp_points_min_dist.  Kept from the reference: a sample without any warped point is skipped (no list entry),
+    and the mean of an empty list is numpy's nan (with its warning)."""
+    repeatability, n_kp_optical, n_kp_thermal = [], [], []
+    pred = config['prediction']
+    for data in dataloader:
+        detection_threshold = pred['detection_threshold']
+        B = data['optical']['image'].shape[0]
+        H_optical = data['optical']['homography'] if 'homography' in data['optical'] else torch.eye(3, 3).repeat(B, 1, 1)
+        H_thermal = data['thermal']['homography'] if 'homography' in data['thermal'] else torch.eye(3, 3).repeat(B, 1, 1)
+        data = utils.data_to_device(data, device)
+        if not net.takes_pair():
+            out_optical, out_thermal = net(data['optical']), net(data['thermal'])
+        else:
+            out_optical, out_thermal, _ = net(data)
+        if pred['nms'] > 0:
+            kw = dict(keep_top_k=pred['topk'], on_cpu=pred.get('cpu_nms', False))
+            out_optical['prob'] = utils.box_nms(out_optical['prob'], pred['nms'], detection_threshold, **kw)
+            out_thermal['prob'] = utils.box_nms(out_thermal['prob'], pred['nms'], detection_threshold, **kw)
+        for (prob_o, prob_t, mask_o, mask_t, h_o, h_t) in zip(out_optical['prob'].split(1), out_thermal['prob'].split(1),
+                                                              data['optical']['valid_mask'].split(1), data['thermal']['valid_mask'].split(1),
+                                                              H_optical.split(1), H_thermal.split(1)):
+            kp_optical_d = torch.nonzero((prob_o.squeeze() > detection_threshold).float() * mask_o.squeeze().to(prob_o.device))
+            kp_thermal_d = torch.nonzero((prob_t.squeeze() > detection_threshold).float() * mask_t.squeeze().to(prob_t.device))
+            n_kp_optical.append(kp_optical_d.shape[0])
+            n_kp_thermal.append(kp_thermal_d.shape[0])
+            kp_optical, kp_thermal = kp_optical_d.cpu().numpy(), kp_thermal_d.cpu().numpy()
+            image_shape = tuple(prob_o.squeeze().shape)
+            h_o32, h_t32 = h_o.squeeze().float().cpu(), h_t.squeeze().float().cpu()
+            warped_optical = warp_keypoints(kp_optical, h_o32.inverse().numpy())
+            warped_optical = warp_keypoints(warped_optical, h_t32.numpy())
+            warped_optical = filter_points(warped_optical, image_shape)
+            warped_thermal = warp_keypoints(kp_thermal, h_t32.inverse().numpy())
+            warped_thermal = warp_keypoints(warped_thermal, h_o32.numpy())
+            warped_thermal = filter_points(warped_thermal, image_shape)
+            N_thermal, N_optical = warped_thermal.shape[0], warped_optical.shape[0]
+            count1 = count2 = 0
+            if kp_optical.shape[0] != 0:
+                count1 = int(np.sum(_min_dist(warped_thermal, kp_optical_d.float()) <= distance_thresh))
+            if kp_thermal.shape[0] != 0:
+                count2 = int(np.sum(_min_dist(warped_optical, kp_thermal_d.float()) <= distance_thresh))
+            if N_thermal + N_optical > 0:
+                repeatability.append((count1 + count2) / (N_thermal + N_optical))
+                if verbose:
+                    print(f"repeatability {repeatability[-1]:.4f} ({count1} + {count2}) / ({N_thermal} + {N_optical})")
+    return np.mean(repeatability), repeatability, n_kp_optical, n_kp_thermal
 
 
 # ------------------------------------------------------------------------------------------------

@@ -43,6 +43,15 @@ def data_unsqueeze(data, dim):
     return data
 
 
+def generate_keypoint_map(keypoints, image_shape):
+    """reference utils.py:121-125: (N, 2) (y, x) points (truncated toward zero by astype(int64)) -> (H, W) bool map.  Indexing is numpy's:
+    a negative coordinate wraps, one beyond the shape raises — callers filter first, as the reference's dataset does."""
+    tmp = np.asarray(keypoints).astype(np.int64).reshape(-1, 2)
+    keypoint_map = np.zeros(image_shape, dtype=bool)
+    keypoint_map[tmp[:, 0], tmp[:, 1]] = True
+    return keypoint_map
+
+
 def fix_model_weigth_keys(weights):
     new_weights = collections.OrderedDict()
     for key, value in weights.items():
