@@ -182,3 +182,66 @@ def test_loss_symbols_exported_and_sized():
     assert b"multiple of 16" in lib.xp_last_error()
     assert lib.xp_detector_loss_fwd(None, None, None, None, 1, 4, 4, 2, 1.0, 0.25, 2.0, None, None, None, None, None, None) != 0
     assert b"kind" in lib.xp_last_error()
+
+
+@pytest.mark.parametrize("key", list(L.EDGE_DESC_CASES))
+def test_edge_descriptor_case_preconditions(key):
+    """every descriptor case of tests/test_gpu_losses_edges.py is a fair test: no dot within 2e-6 x scale^2 of a margin (four times the
+    2^-21 of the split-fp16 dot), no distance within 1e-4 px of the threshold, every sample with a valid pair"""
+    gap, tgap = L.assert_edge_preconditions(key)
+    assert gap >= L.MARGIN_FLOOR == 2e-6 and tgap >= L.THRESHOLD_FLOOR == 1e-4
+    d1, d2, w1, w2, v1, v2, thr = L.edge_desc_inputs(key)
+    ref = L.descriptor_loss64(d1, d2, w1, w2, v1, v2, thr, 1.0, 0.2, 250.0)
+    assert float(ref["norm"].min()) > 0
+    for k in ("sums", "g1", "g2"):
+        assert bool(torch.isfinite(ref[k]).all())
+    c = L.EDGE_DESC_CASES[key]
+    for b, sc in enumerate(c["scales"]):           # the factor really is the sample's scale: unit descriptors times it
+        n1 = d1[b].double().norm(dim=0)
+        assert float((n1 - sc).abs().max()) <= 1e-6 * max(sc, 1e-30), (key, b)
+
+
+def test_edge_table_covers_every_instance_and_shape():
+    rows = L.EDGE_ROWS
+    assert len(rows) == len(set(rows)) == 18
+    assert {16, 32, 48, 80, 96, 144, 176, 192, 208, 240} <= {s[1] for s in rows}
+    assert {1, 5, 32, 33, 128, 129, 133, 256, 385} <= {s[2] * s[3] for s in rows}
+    assert {(d + 63) // 64 * 4 for _, d, _, _ in rows} == {4, 8, 12, 16}                  # every KS instance
+    assert (2, 192, 16, 16) in rows and (1, 192, 25, 41) not in rows
+    for s in rows + [L.EDGE_NEED_ROW]:
+        assert L.EDGE_DESC_CASES[L.row_key(s)]["name"] == "gpu64/" + "_".join(map(str, s))     # what _check_vs_64 names its inputs
+    assert L.EDGE_NEED_ROW[1] == 48 and L.EDGE_NEED_ROW[2] * L.EDGE_NEED_ROW[3] == 129
+    assert L.EDGE_DET_SHAPES == [(1, 1, 1), (3, 16, 17), (2, 9, 57), (5, 4, 4)]
+
+
+def test_threshold_gap_is_the_float32_distance_to_the_threshold():
+    w1 = torch.tensor([[[0.0, 0.0], [3.0, 4.0]]])
+    w2 = torch.tensor([[[0.0, 0.0], [0.0, 9.5]]])
+    assert L.threshold_gap(w1, w2, 8.0) == 1.5             # distances 0, 9.5, 5, sqrt(9 + 30.25) = 6.26..
+    assert L.threshold_gap(w1, w2, 5.0) == 0.0
+    c = L.centres(2, 1, 5)
+    assert L.threshold_gap(c, c, 8.0) == 0.0 and L.threshold_gap(c, c, 12.0) == 4.0
+    assert isinstance(L.threshold_gap(w1.double(), w2.double(), 8.0), float)
+
+
+def test_detector_edge_inputs_hit_their_regimes():
+    """the saturated tensor's regimes as float64 sees them, and the float64 restatement finite there for every focal parameter"""
+    logits, kp, m, noise, label = L.det_saturated()
+    assert torch.equal(label, L.hard_labels(kp, noise))
+    x, lab = logits.reshape(2, 65, -1), label.reshape(2, -1)
+    pred = torch.argmax(torch.softmax(logits, 1), 1).reshape(2, -1)
+    assert bool((x.gather(1, lab[:, None])[:, 0, :64] == 60.0).all()) and bool((pred[:, :64] == lab[:, :64]).all())
+    assert bool((pred[:, 64:128] == (lab[:, 64:128] + 1) % 65).all())
+    assert bool((pred[:, 128:192] == 0).all()) and bool((pred[:, 192:256] == 7).all())
+    for alpha, gamma in L.EDGE_DET_FOCAL:
+        ref = L.detector_loss64(logits, kp, m, noise, 1, 1.0, alpha, gamma)
+        assert all(bool(torch.isfinite(ref[k]).all()) for k in ("total", "dlogits", "loss")), (alpha, gamma)
+        assert float(ref["total"].min()) > 0
+    ce = L.detector_loss64(logits, kp, None, noise, 0, 1.0)
+    per = -torch.log_softmax(logits.double(), 1).gather(1, label[:, None]).squeeze(1).reshape(2, -1)
+    assert float(per[:, :64].max()) < 1e-15 and float(per[:, 64:128].min()) > 50.0
+    assert abs(float(ce["total"].sum()) - float(per.sum())) <= 1e-12 * float(per.sum())
+    kp2, noise2 = L.det_label_ties()
+    ref = L.hard_labels(kp2, noise2)
+    assert int(ref[0, 1, 1]) == 21 and int(ref[1, 2, 3]) == 5 and int(ref[1, 2, 4]) == 64
+    assert float(noise2[1, 5, 2, 4]) < 2.0

@@ -103,13 +103,7 @@ def test_forward_vs_reference(gpu_lib, golden, name):
 
 def _geometry(B, Hc, Wc, seed):
     """the test's own float32 coordinates, handed to both sides: cell centres moved by a smooth field of a few pixels"""
-    c = L.centres(B, Hc, Wc)
-    gen = torch.Generator().manual_seed(seed)
-    w1 = c + 3.0 * torch.rand(B, 1, 2, generator=gen) + 0.01 * c.flip(-1)
-    w2 = c - 2.0 * torch.rand(B, 1, 2, generator=gen) + 0.02 * c
-    v1 = (torch.rand(B, Hc * Wc, generator=gen) > 0.2).float()
-    v2 = (torch.rand(B, Hc * Wc, generator=gen) > 0.1).float()
-    return w1.cuda(), w2.cuda(), v1.cuda(), v2.cuda()
+    return tuple(t.cuda() for t in L.geometry(B, Hc, Wc, seed))
 
 
 def _check_vs_64(B, D, Hc, Wc, need=(True, True), grad=1.0, lam=250.0, thr=8.0, dtype=torch.float32, noncontig=False, tol=TOL):
