@@ -194,24 +194,29 @@ __device__ __forceinline__ void dt_tile(const DtWeights<R>& w, const float* rows
 // Shared staging of one block's chunk(s): pixel indices and the xdbl rows of this route pair.
 // UT: element type of u / xdbl / out in HBM — float, or _Float16 in the fast mixed-precision class (fp16 storage; every value is converted on load, and the
 // conversion on the out_norm store IS the recipe's `y.to(x.dtype)`, VMamba.py:646)
+// T: the chunk length (p.T; a power of two).  Pass 3 hands it in as a compile-time constant, so i / T is a shift there; XW and XD are template
+// constants, so i / XW is a multiply by a reciprocal and the row offset a shift-and-add.  The image's row base and the pair's column offset are
+// taken out of the per-element index.
 template <int R, typename UT = float>
-__device__ __forceinline__ void stage_chunk(const SS2DParams& p, int b, int pair, int chunk0, int* s_pix, int* s_off, float* s_x) {
+__device__ __forceinline__ void stage_chunk(const SS2DParams& p, int T, int b, int pair, int chunk0, int* s_pix, int* s_off, float* s_x) {
     const int L = p.H * p.W;
-    const int npx = p.cpb * p.T;
+    const int npx = p.cpb * T;
+    const int tsh = 31 - __builtin_clz(T);
     for (int i = threadIdx.x; i < npx; i += blockDim.x) {
-        int cl = i / p.T, ii = i - cl * p.T;
+        int cl = i >> tsh, ii = i - (cl << tsh);
         int chunk = chunk0 + cl;
-        const int px = (chunk < p.nc) ? pixel_of(chunk * p.T + ii, L, p.H, p.W, pair == 1) : -1;
+        const int px = (chunk < p.nc) ? pixel_of((chunk << tsh) + ii, L, p.H, p.W, pair == 1) : -1;
         s_pix[i] = px;
         s_off[i] = px >= 0 ? px * p.C : -1;      // element offset of the pixel's row: the step loops address u / ya / out with it (no v_mul_lo_u32 per step)
     }
     __syncthreads();
     constexpr int XW = 2 * (R + 2);
-    const int XD = 2 * XW;
+    constexpr int XD = 2 * XW;
+    const UT* xsrc = reinterpret_cast<const UT*>(p.xdbl) + (int64_t)b * L * XD + pair * XW;
     for (int i = threadIdx.x; i < npx * XW; i += blockDim.x) {
         int pi = i / XW, e = i - pi * XW;
         int px = s_pix[pi];
-        s_x[i] = (px >= 0) ? (float)reinterpret_cast<const UT*>(p.xdbl)[((int64_t)b * L + px) * XD + pair * XW + e] : 0.f;
+        s_x[i] = (px >= 0) ? (float)xsrc[(int64_t)px * XD + e] : 0.f;
     }
     __syncthreads();
 }
@@ -228,7 +233,7 @@ __global__ __launch_bounds__(768) void ss2d_pass1(SS2DParams p) {
     float* s_x = reinterpret_cast<float*>(smem + sizeof(int) * 2 * npx);
     constexpr int XW = 2 * (R + 2);
     const int b = blockIdx.y, pair = blockIdx.z, chunk0 = blockIdx.x * p.cpb;
-    stage_chunk<R, UT>(p, b, pair, chunk0, s_pix, s_off, s_x);
+    stage_chunk<R, UT>(p, p.T, b, pair, chunk0, s_pix, s_off, s_x);
     const int cl = threadIdx.x / p.C, c = threadIdx.x - cl * p.C;
     const int chunk = chunk0 + cl;
     if (chunk >= p.nc) return;
@@ -356,11 +361,18 @@ __global__ __launch_bounds__(64 * P2_G) void ss2d_pass2(SS2DParams p) {
     for (; jj < j1; ++jj) { const int64_t o = off(jj); const float Pj = p.wsP[o], Sj = p.wsS[o]; p.wsS[o] = h; h = fmaf(Pj, h, Sj); }
 }
 
-template <int R, bool COLPAIR, bool FULL, bool AMP = false, typename UT = float>
+// T: the chunk length (= p.T) as a compile-time constant.  A thread loads its chunk's T values of u ONCE, before the forward route, with all loads in
+// flight together, and keeps them in registers: the backward route walks the same pixels and reuses them (it used to load them again, four
+// 4-byte loads and a wait per four steps; in the column traversal consecutive steps are W * C * 4 bytes apart, so each was a fresh line).  The
+// column pair fetches the row pair's partial sums in the same batch, so their latency hides behind the forward route; the row pair keeps its T
+// sums in the registers u leaves and stores them after its last step, outside the dependent chain.  Values, addresses and the order of every
+// floating-point operation are those of the step-by-step form.
+// (COLPAIR stays the second template argument: bench.py tells the row and the column launch apart by the kernel name's first two arguments)
+template <int R, bool COLPAIR, bool FULL, int T, bool AMP = false, typename UT = float>
 __global__ __launch_bounds__(768) void ss2d_pass3(SS2DParams p) {
     constexpr float WL2E = AMP ? 1.f : XP_L2E;
     extern __shared__ __align__(16) char smem[];
-    const int npx = p.cpb * p.T;
+    const int npx = p.cpb * T;
     int* s_pix = reinterpret_cast<int*>(smem);
     int* s_off = s_pix + npx;
     float* s_x = reinterpret_cast<float*>(smem + sizeof(int) * 2 * npx);
@@ -369,11 +381,17 @@ __global__ __launch_bounds__(768) void ss2d_pass3(SS2DParams p) {
     const int SY = p.C + 8;
     const int pair = COLPAIR ? 1 : 0;
     const int b = blockIdx.y, chunk0 = blockIdx.x * p.cpb;
-    stage_chunk<R, UT>(p, b, pair, chunk0, s_pix, s_off, s_x);
+    stage_chunk<R, UT>(p, T, b, pair, chunk0, s_pix, s_off, s_x);
     const int cl = threadIdx.x / p.C, c = threadIdx.x - cl * p.C;
     const int chunk = chunk0 + cl;
     const int L = p.H * p.W;
     if (chunk < p.nc) {
+        const int* so = s_off + cl * T;             // the chunk's pixel row offsets, -1 past the end
+        const float* sx = s_x + cl * T * XW;
+        float* sy = s_y + cl * T * SY + c;
+        const UT* ub = reinterpret_cast<const UT*>(p.u) + (int64_t)b * L * p.C + c;
+        const float* prev = COLPAIR ? (p.ya + (int64_t)b * L * p.C + c) : nullptr;
+        float* dst = COLPAIR ? nullptr : (p.ya + (int64_t)b * L * p.C + c);
         // one route's projection weights live at a time (see pass 1)
         float w0[R];
 #pragma unroll
@@ -381,28 +399,45 @@ __global__ __launch_bounds__(768) void ss2d_pass3(SS2DParams p) {
         const float b0 = WL2E * p.dtb[(pair * 2 + 0) * p.C + c];
         const float A0 = XP_L2E * p.A[(pair * 2 + 0) * p.C + c];
         const float D0 = p.Dp[(pair * 2 + 0) * p.C + c];
-        const UT* ub = reinterpret_cast<const UT*>(p.u) + (int64_t)b * L * p.C + c;
         const int64_t o = ((((int64_t)b * 2 + pair) * p.nc + chunk) * 2) * p.C + c;
         float h = p.wsS[o];
-        // forward route
-        for (int i0 = 0; i0 < p.T; i0 += 4) {
-            float uv[4];
-            int px[4];
+        // the chunk's operands, once for both routes: T (column pair: 2 T) independent loads issued back to back, after the first route's
+        // weights and in the order of their use (the memory counter retires in order: step i waits for u[i] only)
+        float uv[T], pv[COLPAIR ? T : 1];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                px[k] = s_off[cl * p.T + i0 + k];
-                const float t = (XP_SS2D_DBG & 8) ? 1.f : (float)ub[(FULL || px[k] >= 0) ? px[k] : 0];
-                uv[k] = (FULL || px[k] >= 0) ? t : 0.f;
+        for (int i = 0; i < T; ++i) {
+            const int off = so[i];
+            const float t = (XP_SS2D_DBG & 8) ? 1.f : (float)ub[(FULL || off >= 0) ? off : 0];
+            uv[i] = (FULL || off >= 0) ? t : 0.f;
+            if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);      // eight 64-bit addresses at a time, not all T of them before the first load
+        }
+        if (COLPAIR) {
+#pragma unroll
+            for (int i = T - 1; i >= 0; --i) {
+                const int off = so[i];
+                pv[i] = (XP_SS2D_DBG & 2) ? 0.f : prev[(FULL || off >= 0) ? off : 0];
+                if ((i & 7) == 0) __builtin_amdgcn_sched_barrier(0);
             }
+        }
+        // forward route.  Four steps at a time, as before: their operand evaluation (projection, softplus, exp) is independent and interleaves, only
+        // the h update is a chain.  The loops are unrolled because the operands sit in registers; the scheduling barrier after each group keeps
+        // the compiler from interleaving more steps than four (a few registers: 130 -> 126 in the fp16-storage column instance of stage 0, the
+        // difference between three and four waves per SIMD).
+        // A step works on a copy of its u (the empty asm): the compiler evaluates (delta B u, a h) and (D u, C h) as packed pairs with u and h in
+        // an aligned register pair, and without the copy it gives every one of the T held values a pair of its own.
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int pi = cl * p.T + i0 + k;
-                const float* xr = s_x + pi * XW;
+        for (int i0 = 0; i0 < T; i0 += 4) {
+#pragma unroll
+            for (int i = i0; i < i0 + 4; ++i) {
                 float a, bb, cv;
-                step_vals<R, AMP>(xr, w0, b0, A0, uv[k], a, bb, cv);
+                float ui = uv[i];
+                asm("" : "+v"(ui));
+                step_vals<R, AMP>(sx + i * XW, w0, b0, A0, ui, a, bb, cv);
                 h = a * h + bb;
-                s_y[pi * SY + c] = cv * h + D0 * uv[k];   // y = C*h + D*u (csms6s.py:61,67); rows past the end are never read
+                sy[i * SY] = cv * h + D0 * ui;      // y = C*h + D*u (csms6s.py:61,67); rows past the end are never read
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
         // backward route over the same pixels
         asm volatile("" ::: "memory");      // keep the second route's weight loads below the forward loop
@@ -413,30 +448,35 @@ __global__ __launch_bounds__(768) void ss2d_pass3(SS2DParams p) {
         const float A1 = XP_L2E * p.A[(pair * 2 + 1) * p.C + c];
         const float D1 = p.Dp[(pair * 2 + 1) * p.C + c];
         h = p.wsS[o + p.C];
-        const float* prev = COLPAIR ? (p.ya + (int64_t)b * L * p.C + c) : nullptr;
-        float* dst = COLPAIR ? nullptr : (p.ya + (int64_t)b * L * p.C + c);
-        for (int i0 = p.T - 4; i0 >= 0; i0 -= 4) {
-            float uv[4], pv[4];
-            int px[4];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 3; k >= 0; --k) {
-                px[k] = s_off[cl * p.T + i0 + k];
-                const int po = (FULL || px[k] >= 0) ? px[k] : 0;
-                const float t = (XP_SS2D_DBG & 8) ? 1.f : (float)ub[po];
-                uv[k] = (FULL || px[k] >= 0) ? t : 0.f;
-                if (COLPAIR) pv[k] = (XP_SS2D_DBG & 2) ? 0.f : prev[po];
-            }
+        for (int i0 = T - 4; i0 >= 0; i0 -= 4) {
 #pragma unroll
-            for (int k = 3; k >= 0; --k) {
-                const int pi = cl * p.T + i0 + k;
-                const float* xr = s_x + pi * XW + (R + 2);
+            for (int i = i0 + 3; i >= i0; --i) {
                 float a, bb, cv;
-                step_vals<R, AMP>(xr, w1, b1, A1, uv[k], a, bb, cv);
+                float ui = uv[i];
+                asm("" : "+v"(ui));
+                step_vals<R, AMP>(sx + i * XW + (R + 2), w1, b1, A1, ui, a, bb, cv);
                 h = a * h + bb;                                      // u = 0 steps before the image's last pixel keep h = 0
-                const float y2 = cv * h + D1 * uv[k];
-                const float tot = s_y[pi * SY + c] + y2;           // y_fwd + flip(y_bwd)
-                if (COLPAIR) s_y[pi * SY + c] = pv[k] + tot;      // (y0+y2) + (y1+y3)
-                else if (FULL || px[k] >= 0) dst[px[k]] = tot;
+                const float y2 = cv * h + D1 * ui;
+                float tot = sy[i * SY] + y2;                       // y_fwd + flip(y_bwd)
+                if (COLPAIR) sy[i * SY] = pv[i] + tot;            // (y0+y2) + (y1+y3)
+                else {
+                    // u of this step is done with: its register holds the sum until the stores below.  The asm pins the sum to its step: with no
+                    // store in the loop the compiler otherwise sinks the whole h chain below it and carries every step's a, b, C and y_fwd there.
+                    asm volatile("" : "+v"(tot));
+                    uv[i] = tot;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (!COLPAIR) {
+            asm volatile("" ::: "memory");      // read the offsets again here: their T 64-bit store addresses are not carried through both routes
+#pragma unroll
+            for (int i = 0; i < T; ++i) {
+                const int off = so[i];
+                if (FULL || off >= 0) dst[off] = uv[i];
+                if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
@@ -943,6 +983,16 @@ int launch_ss2d_seq(const SS2DParams& p, float* ys, hipStream_t s, bool half_out
     return XP_OK;
 }
 
+// pass 3 by chunk length (a template constant there: the chunk's operands live in registers) and precision class
+template <int R, int T, bool COLPAIR>
+void launch_ss2d_pass3(const SS2DParams& p, dim3 grid, int threads, size_t sm, bool half_io, bool amp, bool full, hipStream_t s) {
+    if (half_io && full) hipLaunchKernelGGL((ss2d_pass3<R, COLPAIR, true, T, true, _Float16>), grid, dim3(threads), sm, s, p);
+    else if (half_io) hipLaunchKernelGGL((ss2d_pass3<R, COLPAIR, false, T, true, _Float16>), grid, dim3(threads), sm, s, p);
+    else if (amp) hipLaunchKernelGGL((ss2d_pass3<R, COLPAIR, false, T, true>), grid, dim3(threads), sm, s, p);
+    else if (full) hipLaunchKernelGGL((ss2d_pass3<R, COLPAIR, true, T>), grid, dim3(threads), sm, s, p);
+    else hipLaunchKernelGGL((ss2d_pass3<R, COLPAIR, false, T>), grid, dim3(threads), sm, s, p);
+}
+
 template <int R>
 int launch_ss2d(const SS2DParams& p, hipStream_t s, bool half_io = false) {
     constexpr int XW = 2 * (R + 2);
@@ -971,19 +1021,15 @@ int launch_ss2d(const SS2DParams& p, hipStream_t s, bool half_io = false) {
     }
     {   // read u, xdbl half; write ya
         XpProfScope prof(("ss2d_pass3_row" + sfx).c_str(), s, el * (2.0 * R + 14.0) / 4.0, 4.0 * (2.0 * MC + MX));
-        if (half_io && full) hipLaunchKernelGGL((ss2d_pass3<R, false, true, true, _Float16>), grid3, dim3(threads), sm3, s, p);
-        else if (half_io) hipLaunchKernelGGL((ss2d_pass3<R, false, false, true, _Float16>), grid3, dim3(threads), sm3, s, p);
-        else if (amp) hipLaunchKernelGGL((ss2d_pass3<R, false, false, true>), grid3, dim3(threads), sm3, s, p);
-        else if (full) hipLaunchKernelGGL((ss2d_pass3<R, false, true>), grid3, dim3(threads), sm3, s, p);
-        else hipLaunchKernelGGL((ss2d_pass3<R, false, false>), grid3, dim3(threads), sm3, s, p);
+        if (p.T == 8) launch_ss2d_pass3<R, 8, false>(p, grid3, threads, sm3, half_io, amp, full, s);
+        else if (p.T == 16) launch_ss2d_pass3<R, 16, false>(p, grid3, threads, sm3, half_io, amp, full, s);
+        else launch_ss2d_pass3<R, 32, false>(p, grid3, threads, sm3, half_io, amp, full, s);
     }
     {   // read u, ya, xdbl half; write out (after out_norm)
         XpProfScope prof(("ss2d_pass3_col_ln" + sfx).c_str(), s, el * (2.0 * R + 14.0) / 4.0, 4.0 * (3.0 * MC + MX));
-        if (half_io && full) hipLaunchKernelGGL((ss2d_pass3<R, true, true, true, _Float16>), grid3, dim3(threads), sm3, s, p);
-        else if (half_io) hipLaunchKernelGGL((ss2d_pass3<R, true, false, true, _Float16>), grid3, dim3(threads), sm3, s, p);
-        else if (amp) hipLaunchKernelGGL((ss2d_pass3<R, true, false, true>), grid3, dim3(threads), sm3, s, p);
-        else if (full) hipLaunchKernelGGL((ss2d_pass3<R, true, true>), grid3, dim3(threads), sm3, s, p);
-        else hipLaunchKernelGGL((ss2d_pass3<R, true, false>), grid3, dim3(threads), sm3, s, p);
+        if (p.T == 8) launch_ss2d_pass3<R, 8, true>(p, grid3, threads, sm3, half_io, amp, full, s);
+        else if (p.T == 16) launch_ss2d_pass3<R, 16, true>(p, grid3, threads, sm3, half_io, amp, full, s);
+        else launch_ss2d_pass3<R, 32, true>(p, grid3, threads, sm3, half_io, amp, full, s);
     }
     XP_LAUNCH_CHECK();
     return XP_OK;
@@ -1046,19 +1092,21 @@ static int ss2d_core_impl(const void* u, const void* xdbl, const float* u32, con
     // chunk length per LAYER (C only, never the batch).  Round 4 re-measured it in the overlapped step instead of alone: 32 pixels at C <= 96, 16 at C = 192 / 384
     // (round 1-3: 16 / 16 / 8, chosen on the stand-alone core) — alone the core times are equal within 2 % at stages 0 - 1, but half as many chunks are half as
     // many workgroups, carry entries and aggregate stores, and with three encoders in flight that is what the step pays for: 1 674 - 1 677 -> 1 707 - 1 708
-    // pairs/s on one box (64 / 32 / 16: 1 662; 64 / 64 / 32: 1 653).  XP_SS2D_TBUDGET / XP_SS2D_T ("96:16,384:8") override for A/B runs.
+    // pairs/s on one box (64 / 32 / 16: 1 662; 64 / 64 / 32: 1 653).  XP_SS2D_TBUDGET / XP_SS2D_T ("96:16,384:8") override for A/B runs
+    // within 8 / 16 / 32 (64, measured slower above, went when pass 3 began to hold a chunk's operands in registers).
     static const int t_budget = getenv("XP_SS2D_TBUDGET") ? atoi(getenv("XP_SS2D_TBUDGET")) : 6144;
     int T = t_budget / (cpb * C);
-    T = T >= 64 ? 64 : (T >= 32 ? 32 : (T >= 16 ? 16 : 8));
+    T = T >= 32 ? 32 : (T >= 16 ? 16 : 8);              // the chunk lengths pass 3 is instantiated for (launch_ss2d_pass3)
     if (!getenv("XP_SS2D_TBUDGET") && cpb == 1 && T > 16) T = 16;          // C = 192: 16 (32 measured equal in the step, slower alone)
     if (const char* tl = getenv("XP_SS2D_T")) {          // experiments: "96:32,192:16,384:16" = chunk length per channel count
         for (const char* q = tl; q && *q;) {
             int cc = 0, tt = 0;
-            if (sscanf(q, "%d:%d", &cc, &tt) == 2 && cc == C && (tt == 8 || tt == 16 || tt == 32 || tt == 64)) T = tt;
+            if (sscanf(q, "%d:%d", &cc, &tt) == 2 && cc == C && (tt == 8 || tt == 16 || tt == 32)) T = tt;
             q = strchr(q, ',');
             if (q) ++q;
         }
     }
+    XP_CHECK_ARG(T == 8 || T == 16 || T == 32, "%s: chunk length %d is not one pass 3 is instantiated for (8, 16, 32)", who, T);
     p.T = T;
     const int L = H * W;
     p.nc = xp_cdiv(L, T);

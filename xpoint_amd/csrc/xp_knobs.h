@@ -37,7 +37,7 @@ static const XpKnob kXpKnobs[] = {
     {"XP_SS2D_SEQ_V1", "ss2d.hip", "1: first sequential kernel (dt projection on the vector ALU)"},
     {"XP_SS2D_SEQ_NW", "ss2d.hip", "waves per route of the pipelined sequential kernel: 1 | 2 | 4"},
     {"XP_SS2D_TBUDGET", "ss2d.hip", "chunk-length budget of the chunked passes (default 6144 pixel-channels)"},
-    {"XP_SS2D_T", "ss2d.hip", "chunk length per channel count, e.g. \"96:32,192:16,384:16\""},
+    {"XP_SS2D_T", "ss2d.hip", "chunk length (8, 16 or 32) per channel count, e.g. \"96:32,192:16,384:16\""},
     {"XP_SS2D_THREADS", "ss2d.hip", "threads per workgroup of the chunked passes (default 192)"},
     {"XP_SCAN_V1", "selective_scan.hip", "force the first d_state = 1 operator-boundary scan kernel"},
     {"XP_SCAN_V2", "selective_scan.hip", "force the second d_state = 1 operator-boundary scan kernel"},
