@@ -349,3 +349,25 @@ def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
         monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
         args = bench.parse()
         assert args.full == ("--full" in argv) and tuple(getattr(args, k) for k in extras) == off, (argv, vars(args))
+
+
+def test_arithmetic_switch_scope_restores_what_it_found():
+    """The forward's scope over the library's process-wide switches (products, engine, amp, override) puts back what it found, also when the call raises."""
+    from xpoint_amd import models
+    lib = _lib.load()
+    get = lambda: (lib.xp_get_dense_products(), lib.xp_get_dense_engine(), lib.xp_get_amp_mode(), lib.xp_get_dense_override())      # noqa: E731
+    before = get()
+    try:
+        _lib.call("xp_set_dense_products", 3)
+        _lib.call("xp_set_dense_engine", 0)
+        with pytest.raises(ZeroDivisionError):
+            with models._arithmetic_class(6, 1, 1, 0x28):
+                assert get() == (6, 1, 1, 0x28)
+                1 / 0
+        assert get() == (3, 0, before[2], 0)      # what it found; the override goes back to 0
+        with models._arithmetic_class(3, 0, before[2], 0):
+            assert get() == (3, 0, before[2], 0)
+        assert get() == (3, 0, before[2], 0)
+    finally:
+        _lib.call("xp_set_dense_products", before[0]); _lib.call("xp_set_dense_engine", before[1]); _lib.call("xp_set_dense_override", before[3])
+    assert get() == before

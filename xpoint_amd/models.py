@@ -9,6 +9,7 @@ There is no CPU path: forward() on CPU tensors raises.
 from __future__ import annotations
 
 import collections
+import contextlib
 import copy
 import ctypes
 import os
@@ -37,6 +38,44 @@ _DENSE_ENGINE = {"h2": 1, "amp16": 1}                                 # gemm_mod
 # at every autocast boundary on the split-fp16 engine, weights of the convolutions / linear layers rounded to fp16 (what autocast casts).
 # "amp16f": the same recipe with HALF STORAGE (xp_xpoint_forward_f16: fp16 tensors in HBM, one-product fp16 MFMA GEMMs, csrc/gemm_f16.hip) — the fast
 # deployment class; same rounding points, same fixture (g20).
+
+
+class _WeightSet:
+    """Device copies of one weight set — one encoder (optical / thermal) in one rounding (plain, or the autocast-cast tensors rounded to fp16): the packed
+    blob and what the library derives from it on the same device (split planes: xp_prepare_split_weights; fp16 copies: xp_prepare_f16_weights)."""
+    __slots__ = ("blob", "split", "f16")
+
+    def __init__(self, blob):
+        self.blob, self.split, self.f16 = blob, None, None
+
+
+@contextlib.contextmanager
+def _arithmetic_class(products: int, engine: int, amp: int, override: int):
+    """The library's process-wide arithmetic switches, set for one (host-synchronous) enqueue and put back to what was found (XP_DENSE_PRODUCTS / an earlier
+    caller), also when the call raises; the override goes back to 0.  They are read when a kernel is launched, so this is not safe against OTHER host
+    threads enqueueing dense kernels at the same time: one enqueueing thread per process (the reference's scripts are single-threaded; multi-GPU = one
+    process per GPU)."""
+    lib = _lib.load()
+    found_products, found_engine, found_amp = int(lib.xp_get_dense_products()), int(lib.xp_get_dense_engine()), int(lib.xp_get_amp_mode())
+    if products != found_products:
+        _lib.call("xp_set_dense_products", products)
+    if engine != found_engine:
+        _lib.call("xp_set_dense_engine", engine)
+    if amp != found_amp:
+        _lib.call("xp_set_amp_mode", amp)
+    if override:
+        _lib.call("xp_set_dense_override", override)
+    try:
+        yield
+    finally:
+        if override:
+            _lib.call("xp_set_dense_override", 0)
+        if amp != found_amp:
+            _lib.call("xp_set_amp_mode", found_amp)
+        if products != found_products:
+            _lib.call("xp_set_dense_products", found_products)
+        if engine != found_engine:
+            _lib.call("xp_set_dense_engine", found_engine)
 
 
 class XPoint(torch.nn.Module):
@@ -71,11 +110,7 @@ class XPoint(torch.nn.Module):
         if self.config['homography_regression_head']['check']:
             assert self.config['takes_pair'], "RegNet can only be used with takes_pair=True"       # XPoint.py:103
         self._ref_state: "collections.OrderedDict[str, torch.Tensor]" = collections.OrderedDict()
-        self._blob: Optional[torch.Tensor] = None        # device-format weights (one float32 tensor); multispectral: the OPTICAL encoder + heads
-        self._wsplit: Optional[torch.Tensor] = None      # split-bf16 copies of the GEMM weights, derived from _blob on the device
-        self._blob_t: Optional[torch.Tensor] = None      # multispectral only: the THERMAL encoder + the same heads
-        self._wsplit_t: Optional[torch.Tensor] = None
-        self._amp_w: Dict[str, tuple] = {}               # gemm_mode "amp16": spectrum -> (blob with the autocast-cast tensors rounded to fp16, its split copies)
+        self._weights: Dict[tuple, _WeightSet] = {}      # (thermal, amp) -> device copies; thermal: multispectral only (that encoder + the same heads)
         # "h2" (default): dense layers on the f16 matrix pipe, f32 operands as two fp16 planes, 3 partial products (f32-grade: operand
         # error <= 2^-23, <= 2^-21 per product worst case, ~2^-25 typical, csrc/gemm_h2_core.h); "x3": bf16 matrix pipe, three exact planes,
         # 6 partial products (f32-grade, no range limit); both are pinned against the reference.  "f32": exact-f32 MFMA kernels;
@@ -187,15 +222,9 @@ class XPoint(torch.nn.Module):
                 t = sd[k]
                 t = torch.from_numpy(np.array(t, copy=True)) if isinstance(t, np.ndarray) else t
                 self._ref_state[k] = t.detach().to("cpu").clone()
-        self._blob = None
-        self._wsplit = None
-        self._blob_t = None
-        self._wsplit_t = None
-        self._amp_w = {}
+        self._drop_weights()
         self._conv_impl = None
         self._regnet_w = None
-        self._h2_off = False              # a new weight set gets the default engine back
-        self._h2_mask = 0
         return _LoadResult(missing, unexpected)
 
     def _bn_affine(self, pre, eps=1e-5):
@@ -291,22 +320,45 @@ class XPoint(torch.nn.Module):
         if self.config['multispectral']:
             raise NotImplementedError("set_weight_blob: multispectral models hold two blobs; load the state_dict on every rank instead")
         assert blob.is_cuda and blob.dtype == torch.float32 and blob.numel() == self.weights_numel()
-        self._blob = blob.contiguous()
-        self._wsplit = None
-        self._amp_w = {}                  # derived copies of the OLD weights (fp16-rounded blob, its split planes) must not survive a new blob
-        self._h2_off = False              # and a new weight set gets the default engine back, as in load_state_dict
-        self._h2_mask = 0
+        self._drop_weights()
+        self._weights[(False, False)] = _WeightSet(blob.contiguous())
         self._device = blob.device
+
+    def _drop_weights(self):
+        """Forget every device copy of the weights (packed blobs, split planes, fp16 copies: nothing derived from an OLD weight set survives a new one) and
+        give the new weight set the default engine back."""
+        self._weights = {}
+        self._h2_off = False
+        self._h2_mask = 0
+
+    def _weight_set(self, thermal: bool, mode: str, dev) -> _WeightSet:
+        """The weight set of one call on `dev` in effective gemm_mode `mode`, with what that mode's entry point reads prepared if missing: the split planes
+        (every mode but "f32" and "amp16f") or the fp16 copies ("amp16f"; converted from the amp blob, whose values are fp16-exact already)."""
+        lib = _lib.load()
+        amp = mode in ("amp16", "amp16f")
+        w = self._weights.get((thermal, amp))
+        if w is None or w.blob.device != dev:
+            if amp and not self._ref_state:
+                raise RuntimeError("gemm_mode 'amp16' needs the reference state dict (load_state_dict): the fp16 rounding of the weights is applied to "
+                                   "the reference tensors, not to the packed blob")
+            spectrum = ("thermal" if thermal else "optical") if self.config['multispectral'] else None
+            w = self._weights[(thermal, amp)] = _WeightSet(self.pack_weights(spectrum, amp=amp).to(dev))
+        if mode == "amp16f" and w.f16 is None:
+            nb = lib.xp_f16_weights_bytes(self._ctx)
+            w.f16 = torch.empty(nb, dtype=torch.uint8, device=dev)
+            _lib.check(lib.xp_prepare_f16_weights(self._ctx, ptr(w.blob), ptr(w.f16), ctypes.c_size_t(nb), _lib.current_stream()), "xp_prepare_f16_weights")
+        if mode not in ("f32", "amp16f") and w.split is None:
+            nb = lib.xp_split_weights_bytes(self._ctx)
+            w.split = torch.empty(nb, dtype=torch.uint8, device=dev)
+            _lib.check(lib.xp_prepare_split_weights(self._ctx, ptr(w.blob), ptr(w.split), ctypes.c_size_t(nb), _lib.current_stream()), "xp_prepare_split_weights")
+        return w
 
     def to(self, device=None, *a, **k):
         if device is not None:
             self._device = torch.device(device)
-            if self._blob is not None and self._blob.device != self._device:
-                self._blob = self._blob.to(self._device)
-                self._wsplit = None
-            if self._blob_t is not None and self._blob_t.device != self._device:
-                self._blob_t = self._blob_t.to(self._device)
-                self._wsplit_t = None
+            for w in self._weights.values():      # blobs move; what was derived from them on the old device is rebuilt on the new one
+                if w.blob.device != self._device:
+                    w.blob, w.split, w.f16 = w.blob.to(self._device), None, None
             self._conv_impl = None          # device copies of the conv-encoder / RegNet weights are rebuilt on the new device
             self._regnet_w = None
             self._ws.clear()
@@ -515,53 +567,12 @@ class XPoint(torch.nn.Module):
                     full[idx_o] = v; full[idx_t] = rt[k]
                     res[k] = full
                 return res
-        if thermal:
-            if self._blob_t is None or self._blob_t.device != dev:
-                self._blob_t = self.pack_weights("thermal").to(dev)
-                self._wsplit_t = None
-        elif self._blob is None or self._blob.device != dev:
-            self._blob = self.pack_weights("optical" if self.config['multispectral'] else None).to(dev)
-            self._wsplit = None
         n, _, H, W = images.shape
         lib = _lib.load()
         if self.gemm_mode not in _DENSE_PRODUCTS:
             raise RuntimeError(f"XPoint.gemm_mode must be one of {sorted(_DENSE_PRODUCTS)}, got {self.gemm_mode!r}")
         mode = self.effective_gemm_mode()
-        split_mode = mode != "f32"
-        amp = mode in ("amp16", "amp16f")
-        fast16 = mode == "amp16f"
-        blob = self._blob_t if thermal else self._blob
-        ws_split = self._wsplit_t if thermal else self._wsplit
-        if amp:
-            key = ("thermal" if thermal else "optical") + str(dev)
-            if key not in self._amp_w:
-                if not self._ref_state:
-                    raise RuntimeError("gemm_mode 'amp16' needs the reference state dict (load_state_dict): the fp16 rounding of the weights is applied to "
-                                       "the reference tensors, not to the packed blob")
-                b16 = self.pack_weights(("thermal" if thermal else "optical") if self.config['multispectral'] else None, amp=True).to(dev)
-                self._amp_w[key] = (b16, None)
-            blob, ws_split = self._amp_w[key]
-        if fast16:
-            # fp16 (N, K) copies of the GEMM weights, converted on the device from the amp blob (whose values are fp16-exact already)
-            k16 = key + "/f16"
-            if k16 not in self._amp_w:
-                nb = lib.xp_f16_weights_bytes(self._ctx)
-                w16 = torch.empty(nb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.xp_prepare_f16_weights(self._ctx, ptr(blob), ptr(w16), ctypes.c_size_t(nb), _lib.current_stream()), "xp_prepare_f16_weights")
-                self._amp_w[k16] = (w16, None)
-            w16 = self._amp_w[k16][0]
-        if split_mode and ws_split is None and not fast16:
-            nb = lib.xp_split_weights_bytes(self._ctx)
-            ws_split = torch.empty(nb, dtype=torch.uint8, device=dev)
-            _lib.check(lib.xp_prepare_split_weights(self._ctx, ptr(blob), ptr(ws_split), ctypes.c_size_t(nb),
-                                                    _lib.current_stream()), "xp_prepare_split_weights")
-            if amp:
-                self._amp_w[key] = (blob, ws_split)
-            elif thermal:
-                self._wsplit_t = ws_split
-            else:
-                self._wsplit = ws_split
-        wsplit = ptr(ws_split) if (split_mode and not fast16) else None
+        w = self._weight_set(thermal, mode, dev)
         Hc = c_i(); Wc = c_i(); Ce = c_i()
         _lib.check(lib.xp_forward_shapes(self._ctx, n, H, W, ctypes.byref(Hc), ctypes.byref(Wc), ctypes.byref(Ce)), "xp_forward_shapes")
         Hc, Wc, Ce = Hc.value, Wc.value, Ce.value
@@ -574,41 +585,17 @@ class XPoint(torch.nn.Module):
         elif tuple(out["enc_nhwc"].shape) != (n, Hc, Wc, Ce) or (want_prob and out.get("prob") is None) or \
                 (want_desc and out.get("desc_nhwc") is None) or (want_logits and out.get("logits_nhwc") is None):
             raise RuntimeError("forward_raw(out=...): buffers do not match this call")
-        # the precision class is process-wide in the library and read when a kernel is launched: set for the duration of this
-        # (host-synchronous) enqueue, then back to the default.  Not safe against OTHER host threads enqueueing dense kernels at the
-        # same time: one enqueueing thread per process (the reference's scripts are single-threaded; multi-GPU = one process per GPU)
-        if fast16:      # its own entry point: no process-wide switches involved
-            _lib.check(lib.xp_xpoint_forward_f16(self._ctx, ptr(blob), ptr(w16), ptr(images), n, H, W, ptr(ws), ctypes.c_size_t(ws.numel()),
+        word = ptr(self.status_word(dev) if status is None else status)
+        if mode == "amp16f":      # its own entry point: no process-wide switches involved
+            _lib.check(lib.xp_xpoint_forward_f16(self._ctx, ptr(w.blob), ptr(w.f16), ptr(images), n, H, W, ptr(ws), ctypes.c_size_t(ws.numel()),
                                                  ptr(out["prob"]), ptr(out["desc_nhwc"]), ptr(out["enc_nhwc"]), ptr(out["logits_nhwc"]),
-                                                 ptr(self.status_word(dev) if status is None else status), _lib.current_stream()), "xp_xpoint_forward_f16")
+                                                 word, _lib.current_stream()), "xp_xpoint_forward_f16")
             return out
-        nprod = _DENSE_PRODUCTS[mode]
-        engine = _DENSE_ENGINE.get(mode, 0)
-        prev = int(lib.xp_get_dense_products())          # whatever XP_DENSE_PRODUCTS / an earlier caller left: restored afterwards
-        prev_engine = int(lib.xp_get_dense_engine())
-        if nprod != prev:
-            _lib.call("xp_set_dense_products", nprod)
-        if engine != prev_engine:
-            _lib.call("xp_set_dense_engine", engine)
-        prev_amp = int(lib.xp_get_amp_mode())
-        if int(amp) != prev_amp:
-            _lib.call("xp_set_amp_mode", int(amp))
-        ovmask = self._h2_mask if mode == "h2" else 0          # launches of THIS weight set that left the fp16 range (handle_status)
-        if ovmask:
-            _lib.call("xp_set_dense_override", ovmask)
-        try:
-            _lib.check(lib.xp_xpoint_forward_ex(self._ctx, ptr(blob), wsplit, ptr(images), n, H, W, ptr(ws), ctypes.c_size_t(ws.numel()),
-                                                ptr(out["prob"]), ptr(out["desc_nhwc"]), ptr(out["enc_nhwc"]), ptr(out["logits_nhwc"]),
-                                                ptr(self.status_word(dev) if status is None else status), _lib.current_stream()), "xp_xpoint_forward_ex")
-        finally:
-            if ovmask:
-                _lib.call("xp_set_dense_override", 0)
-            if int(amp) != prev_amp:
-                _lib.call("xp_set_amp_mode", prev_amp)
-            if nprod != prev:
-                _lib.call("xp_set_dense_products", prev)
-            if engine != prev_engine:
-                _lib.call("xp_set_dense_engine", prev_engine)
+        # override: the launches of THIS weight set that left the fp16 range (handle_status)
+        with _arithmetic_class(_DENSE_PRODUCTS[mode], _DENSE_ENGINE.get(mode, 0), int(mode == "amp16"), self._h2_mask if mode == "h2" else 0):
+            _lib.check(lib.xp_xpoint_forward_ex(self._ctx, ptr(w.blob), None if mode == "f32" else ptr(w.split), ptr(images), n, H, W, ptr(ws),
+                                                ctypes.c_size_t(ws.numel()), ptr(out["prob"]), ptr(out["desc_nhwc"]), ptr(out["enc_nhwc"]),
+                                                ptr(out["logits_nhwc"]), word, _lib.current_stream()), "xp_xpoint_forward_ex")
         return out
 
     @staticmethod
