@@ -612,6 +612,50 @@ int xp_detector_loss_bwd(const float* logits, const int* labels, const float* va
                          float dustbin_weight, float alpha, float gamma, float* dlogits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training-pair augmentation (reference xpoint/datasets/augmentation/; xpoint_amd/augmentation.py drives these; csrc/augment.hip).
+ * All images are (B, H, W) f32, one channel; every call is one launch sequence for the whole batch.  H, W < 32768, H * W <= 2^30.
+ *   xp_aug_warp: cv2.warpPerspective(image, Hm, (W, H), INTER_LINEAR, borderMode) with the f32 arithmetic of xp_warp_perspective;
+ *     border_reflect == 0: BORDER_CONSTANT (bit-equal to xp_warp_perspective), else BORDER_REFLECT_101 (cv::borderInterpolate per
+ *     tap; a dimension of 1 gives 0).  Hm (B, 9) f64 forward maps.  warp (B) u8 or NULL (= all set): a sample with warp[b] == 0 is
+ *     copied, and mask[b] (mask (B, H, W) u8 or NULL, filled by xp_ha_valid_mask BEFORE this call) is set to all ones.
+ *   xp_aug_scatter_labels: kp_out = generate_keypoint_map(filter_points(warp_keypoints(nonzero(kp_in), Hm))): (x', y') =
+ *     trunc((X / W, Y / W)) in f64, kept when inside after the truncation toward zero; kp_out is cleared first.  warp[b] == 0 copies.
+ *   xp_aug_random_field: out (B, npix) f32, element p of field b from Philox4x32-10 with counter (p, 0, 0, seed >> 32) and key
+ *     (seed & 0xffffffff, sample_ids[b] * 8 + primitive): XP_AUG_FIELD_UNIFORM (x0 >> 8) * 2^-24, XP_AUG_FIELD_NORMAL
+ *     sqrt(-2 ln(1 - u0)) cos(2 pi u1).  sample_ids (B) int32 on the device, < 2^29.
+ *   xp_aug_photo_prologue: partials (B, xp_aug_partials_per_sample(H, W)) f64 partial sums of the images; shade (B, H, W) f32 or
+ *     NULL: the 0/1 union of n_ellipses rotated ellipses per sample, ellipses (B, n_ellipses, 6) f64 = (cx, cy, a, b, cos, sin),
+ *     inside iff ((dx cos + dy sin) / a)^2 + ((dy cos - dx sin) / b)^2 <= 1 in f64.
+ *   xp_aug_blur: one pass (vertical != 0: along y) of a separable filter behind BORDER_REFLECT_101 (any radius); weights (B, kmax)
+ *     f32, ksizes (B) int32 in 1..kmax, odd.
+ *   xp_aug_photo_step: step `step` of every sample's program: ops (B, n_steps) int32 XP_AUG_* opcodes, params (B, n_steps) f32 (stddev,
+ *     prob, delta, strength, transparency, motion ksize <= 11).  partials_in: the partial sums of src (from the prologue or the previous
+ *     step; read by XP_AUG_CONTRAST in a fixed order); partials_out: those of dst.  shade: the blurred mask (XP_AUG_SHADE);
+ *     motion_kernels (B, 121) f32 row-major ksize x ksize (XP_AUG_MOTION_BLUR: cv2.filter2D, correlation, centre anchor,
+ *     BORDER_REFLECT_101); field_gauss / field_speckle (B, H, W) f32 or NULL = generated as xp_aug_random_field does with primitive = the
+ *     opcode.  A step whose table is NULL, or whose opcode is unknown, copies. */
+#define XP_AUG_GAUSSIAN_NOISE 0
+#define XP_AUG_SPECKLE_NOISE 1
+#define XP_AUG_BRIGHTNESS 2
+#define XP_AUG_CONTRAST 3
+#define XP_AUG_SHADE 4
+#define XP_AUG_MOTION_BLUR 5
+#define XP_AUG_FIELD_UNIFORM 0
+#define XP_AUG_FIELD_NORMAL 1
+int xp_aug_partials_per_sample(int H, int W);
+int xp_aug_warp(const float* src, float* dst, const double* Hm, const uint8_t* warp, uint8_t* mask, int B, int H, int W, int border_reflect,
+                void* stream);
+int xp_aug_scatter_labels(const uint8_t* kp_in, uint8_t* kp_out, const double* Hm, const uint8_t* warp, int B, int H, int W, void* stream);
+int xp_aug_random_field(float* out, unsigned long long seed, const int* sample_ids, int primitive, int kind, int B, int npix, void* stream);
+int xp_aug_photo_prologue(const float* images, double* partials, const double* ellipses, float* shade, int n_ellipses, int B, int H, int W,
+                          void* stream);
+int xp_aug_blur(const float* src, float* dst, const float* weights, const int* ksizes, int kmax, int B, int H, int W, int vertical,
+                void* stream);
+int xp_aug_photo_step(const float* src, float* dst, const int* ops, const float* params, int step, int n_steps, const double* partials_in,
+                      double* partials_out, const float* shade, const float* motion_kernels, const float* field_gauss,
+                      const float* field_speckle, unsigned long long seed, const int* sample_ids, int B, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -1,0 +1,327 @@
+"""The training-pair augmentation restated in numpy (numpy only: it runs wherever the tests run), the yardstick of
+tests/test_cpu_augmentation.py and tests/test_gpu_augmentation.py.
+
+Everything that is integer-valued in the reference (source coordinates of the warps, the valid mask, the label maps, speckle positions,
+the Philox words) is restated with the device's operation order, so the comparison is equality; everything real-valued (the photometric
+chain) is restated in f64, as the reference carries it, and compared to 1e-4.  OpenCV is absent: its routines are restated from their
+published definitions (borderInterpolate, warpPerspective's 1/32-pixel remap, filter2D = correlation with a centre anchor,
+GaussianBlur's getGaussianKernel), cv2.ellipse by the analytic inside test (a stated difference, xpoint_amd/augmentation.py)."""
+import numpy as np
+
+PRIMITIVES = ['additive_gaussian_noise', 'additive_speckle_noise', 'random_brightness', 'random_contrast', 'additive_shade', 'motion_blur']
+
+
+# ----------------------------------------------------------------------------------------------- borders and warps
+def border_interpolate_101(p, length):
+    """cv::borderInterpolate(p, len, BORDER_REFLECT_101), the loop as OpenCV writes it (delta = 1), elementwise."""
+    p = np.array(p, dtype=np.int64, copy=True)
+    if length == 1:
+        return np.zeros_like(p)
+    while True:
+        bad = (p < 0) | (p >= length)
+        if not bad.any():
+            return p
+        p = np.where(bad & (p < 0), -p - 1 + 1, np.where(bad, length - 1 - (p - length) - 1, p))
+
+
+def cv_invert3(S):
+    """OpenCV's closed 3 x 3 inverse in double, in the operand order of csrc/xp_common.h: xp_cv_invert3."""
+    S = np.asarray(S, np.float64).reshape(9)
+    d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6])
+    if d == 0.0:
+        return np.zeros(9)
+    d = 1.0 / d
+    return np.array([(S[4] * S[8] - S[5] * S[7]) * d, (S[2] * S[7] - S[1] * S[8]) * d, (S[1] * S[5] - S[2] * S[4]) * d,
+                     (S[5] * S[6] - S[3] * S[8]) * d, (S[0] * S[8] - S[2] * S[6]) * d, (S[2] * S[3] - S[0] * S[5]) * d,
+                     (S[3] * S[7] - S[4] * S[6]) * d, (S[1] * S[6] - S[0] * S[7]) * d, (S[0] * S[4] - S[1] * S[3]) * d])
+
+
+def _fixed_point_source(Hm, h, w, scale):
+    """WarpPerspectiveInvoker's integer source coordinates of every destination pixel: scale = 32 (INTER_LINEAR, 1/32 pixel) or 1
+    (INTER_NEAREST).  The row base is formed at the first column of the pixel's block, the in-block offset added afterwards."""
+    m = cv_invert3(Hm)
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    bw = min(64, w) if h >= 16 else min(w, 1024 // h)
+    xb = (x // bw * bw).astype(np.float64)
+    x1 = x.astype(np.float64) - xb
+    y = y.astype(np.float64)
+    X0 = m[0] * xb + m[1] * y + m[2]
+    Y0 = m[3] * xb + m[4] * y + m[5]
+    W0 = m[6] * xb + m[7] * y + m[8]
+    W = W0 + m[6] * x1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        W = np.where(W != 0.0, scale / W, 0.0)
+        fX = np.maximum(-2147483648.0, np.minimum(2147483647.0, (X0 + m[0] * x1) * W))
+        fY = np.maximum(-2147483648.0, np.minimum(2147483647.0, (Y0 + m[3] * x1) * W))
+    return np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)          # round half to even, as lrint
+
+
+def warp_perspective_f32(image, Hm, border_reflect):
+    """cv2.warpPerspective(image f32 (h, w), Hm, (w, h), INTER_LINEAR, BORDER_REFLECT_101 | BORDER_CONSTANT) in the f32 arithmetic of
+    csrc/warp.hip: returns f32, to be compared for equality."""
+    image = np.asarray(image, np.float32)
+    h, w = image.shape
+    X, Y = _fixed_point_source(Hm, h, w, 32.0)
+    sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
+    fx, fy = (X & 31).astype(np.float32) * np.float32(0.03125), (Y & 31).astype(np.float32) * np.float32(0.03125)
+    one = np.float32(1)
+
+    def tap(xx, yy):
+        if border_reflect:
+            return image[border_interpolate_101(yy, h), border_interpolate_101(xx, w)]
+        inside = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+        return np.where(inside, image[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)], np.float32(0))
+
+    t0, t1, t2, t3 = tap(sx, sy), tap(sx + 1, sy), tap(sx, sy + 1), tap(sx + 1, sy + 1)
+    w0, w1, w2, w3 = (one - fy) * (one - fx), (one - fy) * fx, fy * (one - fx), fy * fx
+    out = ((t0 * w0 + t1 * w1) + t2 * w2) + t3 * w3
+    assert out.dtype == np.float32
+    return out
+
+
+def compute_valid_mask(shape, Hm, erosion_radius=0, mask_border=False):
+    """reference homographies.py: compute_valid_mask: the INTER_NEAREST warp of ones, then the (2r+1)^2 erosion behind a zero frame
+    (mask_border) or cv2.erode's default border, which never erodes."""
+    h, w = shape
+    X, Y = _fixed_point_source(Hm, h, w, 1.0)
+    mask = ((X >= 0) & (X < w) & (Y >= 0) & (Y < h)).astype(np.uint8)
+    r = int(erosion_radius)
+    if r > 0:
+        pad = np.full((h + 2 * r, w + 2 * r), 0 if mask_border else 1, np.uint8)
+        pad[r:r + h, r:r + w] = mask
+        out = np.ones((h, w), np.uint8)
+        for dy in range(2 * r + 1):
+            for dx in range(2 * r + 1):
+                out = np.minimum(out, pad[dy:dy + h, dx:dx + w])
+        mask = out
+    return mask.astype(bool)
+
+
+# ----------------------------------------------------------------------------------------------- labels
+def warp_keypoints(keypoints, Hm):
+    """reference homographies.py: warp_keypoints: (y, x) rows -> [x', y', w'] = H [x, y, 1], divided in f64, .astype(int) (truncation
+    toward zero).  Returned as f64 AFTER the truncation (a non-finite quotient has no integer value: it stays non-finite and is filtered)."""
+    Hm = np.asarray(Hm, np.float64).reshape(3, 3)
+    kp = np.asarray(keypoints, np.float64).reshape(-1, 2)
+    x, y = kp[:, 1], kp[:, 0]
+    X = (Hm[0, 0] * x + Hm[0, 1] * y) + Hm[0, 2]
+    Y = (Hm[1, 0] * x + Hm[1, 1] * y) + Hm[1, 2]
+    W = (Hm[2, 0] * x + Hm[2, 1] * y) + Hm[2, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.stack([np.trunc(Y / W), np.trunc(X / W)], 1)
+
+
+def warp_keypoints_exact(keypoints, Hm):
+    """the quotients before the truncation, (y', x') rows"""
+    Hm = np.asarray(Hm, np.float64).reshape(3, 3)
+    kp = np.asarray(keypoints, np.float64).reshape(-1, 2)
+    x, y = kp[:, 1], kp[:, 0]
+    W = (Hm[2, 0] * x + Hm[2, 1] * y) + Hm[2, 2]
+    return np.stack([((Hm[1, 0] * x + Hm[1, 1] * y) + Hm[1, 2]) / W, ((Hm[0, 0] * x + Hm[0, 1] * y) + Hm[0, 2]) / W], 1)
+
+
+def filter_points(points, shape):
+    p = np.asarray(points, np.float64).reshape(-1, 2)
+    keep = (p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 0] < shape[0]) & (p[:, 1] < shape[1])          # NaN / inf compare False
+    return p[keep]
+
+
+def generate_keypoint_map(points, shape):
+    out = np.zeros(shape, bool)
+    p = np.asarray(points).reshape(-1, 2).astype(np.int64)
+    out[p[:, 0], p[:, 1]] = True
+    return out
+
+
+def warp_label_map(label_map, Hm):
+    kp = np.stack(np.nonzero(np.asarray(label_map)), 1)
+    return generate_keypoint_map(filter_points(warp_keypoints(kp, Hm), label_map.shape), label_map.shape)
+
+
+# ----------------------------------------------------------------------------------------------- photometric primitives (f64)
+def additive_gaussian_noise(image, stddev, z):
+    """z: the standard-normal field; np.random.normal(0, stddev, shape) is 0 + stddev * z of the same stream"""
+    return np.clip(np.asarray(image, np.float64) + np.float64(stddev) * np.asarray(z, np.float64), 0.0, 1.0)
+
+
+def additive_speckle_noise(image, prob, u):
+    """The comparison runs in the dtype the field and prob arrive in (f64 from the reference's stream, f32 on the device)."""
+    out = np.array(image, dtype=np.float64, copy=True)
+    u = np.asarray(u)
+    prob = u.dtype.type(prob)
+    out[u < prob] = 0.0
+    out[u > (u.dtype.type(1.0) - prob)] = 1.0
+    return out
+
+
+def speckle_positions(prob, u):
+    u = np.asarray(u)
+    prob = u.dtype.type(prob)
+    return u < prob, u > (u.dtype.type(1.0) - prob)
+
+
+def random_brightness(image, delta):
+    return np.clip(np.asarray(image, np.float64) + np.float64(delta), 0.0, 1.0)
+
+
+def random_contrast(image, strength):
+    image = np.asarray(image, np.float64)
+    mean = image.mean()
+    return np.clip((image - mean) * np.float64(strength) + mean, 0.0, 1.0)
+
+
+def motion_blur_kernel(mode, ksize):
+    """the reference's kernel: a line (h, v, diag_down, diag_up) times a Gaussian of variance ksize^2 / 16, normalised"""
+    center = int((ksize - 1) / 2)
+    kernel = np.zeros((ksize, ksize))
+    if mode == 'h':
+        kernel[center, :] = 1.
+    elif mode == 'v':
+        kernel[:, center] = 1.
+    elif mode == 'diag_down':
+        kernel = np.eye(ksize)
+    elif mode == 'diag_up':
+        kernel = np.flip(np.eye(ksize), 0)
+    else:
+        raise ValueError(mode)
+    var = ksize * ksize / 16.0
+    grid = np.repeat(np.arange(ksize)[:, np.newaxis], ksize, axis=-1)
+    gaussian = np.exp(-(np.square(grid - center) + np.square(grid.T - center)) / (2.0 * var))
+    kernel = kernel * gaussian
+    return kernel / np.sum(kernel)
+
+
+def filter2d(image, kernel):
+    """cv2.filter2D(image, -1, kernel): correlation, anchor at the kernel centre, BORDER_REFLECT_101"""
+    image = np.asarray(image, np.float64)
+    kernel = np.asarray(kernel, np.float64)
+    h, w = image.shape
+    kh, kw = kernel.shape
+    out = np.zeros((h, w))
+    ys, xs = np.arange(h), np.arange(w)
+    for dy in range(kh):
+        yy = border_interpolate_101(ys + dy - kh // 2, h)
+        for dx in range(kw):
+            if kernel[dy, dx] != 0.0:
+                xx = border_interpolate_101(xs + dx - kw // 2, w)
+                out += kernel[dy, dx] * image[np.ix_(yy, xx)]
+    return out
+
+
+def gaussian_kernel(ksize):
+    """cv2.getGaussianKernel(ksize, sigma <= 0): sigma = 0.3 ((ksize - 1) 0.5 - 1) + 0.8, normalised in double.  (OpenCV substitutes
+    fixed tables for ksize <= 7 with sigma <= 0; the formula is used for every size here: a stated difference of < 4e-3 per weight at
+    sizes the reference's kernel_size_range [250, 350] never reaches.)"""
+    sigma = 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8
+    x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+    k = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return k / k.sum()
+
+
+def gaussian_blur(image, ksize):
+    k = gaussian_kernel(ksize)
+    return filter2d(filter2d(image, k[None, :]), k[:, None])
+
+
+def ellipse_table(ellipses):
+    """(n, 5) rows (cx, cy, ax, ay, angle in degrees) -> (n, 6) f64 rows (cx, cy, a, b, cos, sin); a zero half axis is widened to half a
+    pixel, so it still covers its centre line"""
+    e = np.asarray(ellipses, np.float64).reshape(-1, 5)
+    ang = np.deg2rad(e[:, 4])
+    return np.stack([e[:, 0], e[:, 1], np.maximum(e[:, 2], 0.5), np.maximum(e[:, 3], 0.5), np.cos(ang), np.sin(ang)], 1)
+
+
+def ellipse_mask(shape, table):
+    """union of the filled rotated ellipses by the analytic inside test, in f64 with the device's operation order"""
+    h, w = shape
+    yd, xd = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    m = np.zeros((h, w), np.float64)
+    for q in np.asarray(table, np.float64).reshape(-1, 6):
+        dx, dy = xd - q[0], yd - q[1]
+        u, v = (dx * q[4] + dy * q[5]) / q[2], (dy * q[4] - dx * q[5]) / q[3]
+        m[u * u + v * v <= 1.0] = 1.0
+    return m
+
+
+def additive_shade(image, table, transparency, ksize):
+    mask = gaussian_blur(ellipse_mask(np.asarray(image).shape, table), ksize)
+    return np.clip(np.asarray(image, np.float64) * (1 - np.float64(transparency) * mask), 0, 1.0)
+
+
+def run_program(image, prog, i, fields):
+    """sample i of the tables `sample_photometric_params` emits, with the fields given per primitive name as (B, h, w) arrays"""
+    out = np.asarray(image, np.float64)
+    for s, op in enumerate(prog['ops'][i]):
+        name, par = PRIMITIVES[int(op)], prog['params'][i, s]
+        if name == 'additive_gaussian_noise':
+            out = additive_gaussian_noise(out, par, fields[name][i])
+        elif name == 'additive_speckle_noise':
+            out = additive_speckle_noise(out, par, fields[name][i])
+        elif name == 'random_brightness':
+            out = random_brightness(out, par)
+        elif name == 'random_contrast':
+            out = random_contrast(out, par)
+        elif name == 'additive_shade':
+            out = additive_shade(out, prog['ellipses'][i], par, int(prog['shade_ksize'][i]))
+        else:
+            ks = int(par)
+            out = filter2d(out, np.asarray(prog['motion_kernel'][i, :ks * ks], np.float64).reshape(ks, ks))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- generator
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11).  counter (..., 4), key (..., 2)
+    uint32 -> (..., 4) uint32."""
+    c = [np.asarray(counter[..., k], np.uint64) for k in range(4)]
+    k0, k1 = np.asarray(key[..., 0], np.uint64), np.asarray(key[..., 1], np.uint64)
+    M0, M1, W0, W1, lo = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85), np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = M0 * c[0], M1 * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & lo, (p0 >> s32) ^ c[3] ^ k1, p0 & lo]
+        k0, k1 = (k0 + W0) & lo, (k1 + W1) & lo
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def philox_words(seed, sample_id, primitive, npix):
+    """the device's words of one sample's field: counter (pixel, 0, 0, seed >> 32), key (seed & 0xffffffff, sample_id * 8 + primitive)"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.zeros((npix, 4), np.uint32)
+    ctr[:, 0] = np.arange(npix, dtype=np.uint32)
+    ctr[:, 3] = seed >> 32
+    key = np.broadcast_to(np.array([seed & 0xFFFFFFFF, (int(sample_id) * 8 + int(primitive)) & 0xFFFFFFFF], np.uint32), (npix, 2))
+    return philox4x32_10(ctr, key)
+
+
+def uniform_from_words(words):
+    """(x >> 8) * 2^-24: exact in f32"""
+    return ((words >> np.uint32(8)).astype(np.float64) * 2.0 ** -24)
+
+
+def uniform_field(seed, sample_id, primitive, npix):
+    return uniform_from_words(philox_words(seed, sample_id, primitive, npix)[:, 0]).astype(np.float32)
+
+
+def normal_field_f64(seed, sample_id, primitive, npix):
+    """Box-Muller in f64 on the device's uniforms: sqrt(-2 ln(1 - u0)) cos(2 pi u1)"""
+    wds = philox_words(seed, sample_id, primitive, npix)
+    u0, u1 = uniform_from_words(wds[:, 0]), uniform_from_words(wds[:, 1])
+    return np.sqrt(-2.0 * np.log(1.0 - u0)) * np.cos(2.0 * np.pi * u1)
+
+
+# ----------------------------------------------------------------------------------------------- homography-head input
+def prep_hm_regression_input(optical, thermal, optical_H, thermal_H, h, w, patch=128):
+    """reference ImagePairDataset.prep_hm_regression_input with its quirks: the corner (h // 2 - 64, w // 2 - 64) is used as (x, y), the
+    perturbed points are optical_H @ thermal_H @ p WITHOUT the projective division, truncated by int().  optical / thermal (h, w)."""
+    tl = np.array([h // 2 - 64, w // 2 - 64])
+    four = [tl, tl + [patch, 0], tl + [patch, patch], tl + [0, patch]]
+    M = np.asarray(optical_H, np.float64).reshape(3, 3) @ np.asarray(thermal_H, np.float64).reshape(3, 3)
+    pert = []
+    for p in four:
+        q = M @ np.array([[p[0]], [p[1]], [1]], np.float64)
+        pert.append([int(q[0, 0]), int(q[1, 0])])
+    four_points = np.subtract(np.array(pert), np.array(four))
+    xs, ys = [p[0] for p in four], [p[1] for p in four]
+    crop = np.stack([np.asarray(optical)[min(ys):max(ys), min(xs):max(xs)], np.asarray(thermal)[min(ys):max(ys), min(xs):max(xs)]], 0)
+    return crop, four_points

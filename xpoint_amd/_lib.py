@@ -118,6 +118,12 @@ _SIGNATURES = {
     "xp_descriptor_loss_bwd": [c_p] + [c_i] * 4 + [c_f] * 4 + [c_p, c_sz, c_p, c_p, c_p],
     "xp_detector_loss_fwd": [c_p] * 4 + [c_i] * 4 + [c_f] * 3 + [c_p] * 6,
     "xp_detector_loss_bwd": [c_p] * 4 + [c_i] * 4 + [c_f] * 3 + [c_p] * 2,
+    "xp_aug_warp": [c_p] * 5 + [c_i] * 4 + [c_p],
+    "xp_aug_scatter_labels": [c_p] * 4 + [c_i] * 3 + [c_p],
+    "xp_aug_random_field": [c_p, ctypes.c_uint64, c_p] + [c_i] * 4 + [c_p],
+    "xp_aug_photo_prologue": [c_p] * 4 + [c_i] * 4 + [c_p],
+    "xp_aug_blur": [c_p] * 4 + [c_i] * 5 + [c_p],
+    "xp_aug_photo_step": [c_p] * 4 + [c_i, c_i] + [c_p] * 6 + [ctypes.c_uint64, c_p] + [c_i] * 3 + [c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -157,6 +163,7 @@ _SIZE_QUERIES = {
     "xp_match_workspace_bytes": (c_sz, [c_i] * 4),
     "xp_match_cand_cap": (c_i, []),
     "xp_extract_keypoints_workspace_bytes": (c_sz, [c_i] * 3),
+    "xp_aug_partials_per_sample": (c_i, [c_i] * 2),
 }
 
 

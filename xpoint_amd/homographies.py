@@ -136,6 +136,21 @@ def sample_homography(image_shape, perspective=True, scaling=True, rotation=True
     return get_perspective_transform((pts1 * shape).astype(np.float32), (pts2 * shape).astype(np.float32))
 
 
+def sample_homography_corner(image_shape, config):
+    """reference homographies.py:455-477 (the homography head's training pairs): a patch_size square at a random position at least rho
+    from the border, its four corners perturbed by up to rho pixels each; returns the INVERSE of the map patch corners -> perturbed
+    corners (float64 3 x 3).  The draws come from Python's `random` in the reference's order: position x, position y, then (dx, dy) of
+    the top-left, top-right, bottom-right and bottom-left corner.  image_shape = (h, w); config = {'rho', 'patch_size'}."""
+    import random
+    imsize = image_shape[1], image_shape[0]
+    rho, patch_size = int(config["rho"]), int(config["patch_size"])
+    position_p = (random.randint(rho, imsize[0] - rho - patch_size), random.randint(rho, imsize[1] - rho - patch_size))
+    four_points = [position_p, (patch_size + position_p[0], position_p[1]), (patch_size + position_p[0], patch_size + position_p[1]),
+                   (position_p[0], patch_size + position_p[1])]
+    perturbed = [(p[0] + random.randint(-rho, rho), p[1] + random.randint(-rho, rho)) for p in four_points]
+    return np.linalg.inv(get_perspective_transform(np.float32(four_points), np.float32(perturbed)))
+
+
 # ------------------------------------------------------------------------------------------------ kornia 0.1.4 matrix chain (host, f32)
 def _normal_transform_pixel(h, w):
     n = torch.tensor([[1.0, 0.0, -1.0], [0.0, 1.0, -1.0], [0.0, 0.0, 1.0]])
