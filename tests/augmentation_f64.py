@@ -4,97 +4,16 @@ tests/test_cpu_augmentation.py and tests/test_gpu_augmentation.py.
 Everything that is integer-valued in the reference (source coordinates of the warps, the valid mask, the label maps, speckle positions,
 the Philox words) is restated with the device's operation order, so the comparison is equality; everything real-valued (the photometric
 chain) is restated in f64, as the reference carries it, and compared to 1e-4.  OpenCV is absent: its routines are restated from their
-published definitions (borderInterpolate, warpPerspective's 1/32-pixel remap, filter2D = correlation with a centre anchor,
-GaussianBlur's getGaussianKernel), cv2.ellipse by the analytic inside test (a stated difference, xpoint_amd/augmentation.py)."""
+published definitions (borderInterpolate and warpPerspective's 1/32-pixel remap in oracle/cv_restated.py, filter2D = correlation with a
+centre anchor, GaussianBlur's getGaussianKernel), cv2.ellipse by the analytic inside test (a stated difference, xpoint_amd/augmentation.py)."""
 import numpy as np
 
+# OpenCV's warpPerspective scheme (borders, warps, the valid mask) is oracle/cv_restated.py, shared with tools/make_golden_ha.py; the names
+# the tests use stay
+from oracle.cv_restated import (border_interpolate_101, compute_valid_mask, cv_invert3, warp_perspective_f32,  # noqa: F401
+                                fixed_point_source as _fixed_point_source)
+
 PRIMITIVES = ['additive_gaussian_noise', 'additive_speckle_noise', 'random_brightness', 'random_contrast', 'additive_shade', 'motion_blur']
-
-
-# ----------------------------------------------------------------------------------------------- borders and warps
-def border_interpolate_101(p, length):
-    """cv::borderInterpolate(p, len, BORDER_REFLECT_101), the loop as OpenCV writes it (delta = 1), elementwise."""
-    p = np.array(p, dtype=np.int64, copy=True)
-    if length == 1:
-        return np.zeros_like(p)
-    while True:
-        bad = (p < 0) | (p >= length)
-        if not bad.any():
-            return p
-        p = np.where(bad & (p < 0), -p - 1 + 1, np.where(bad, length - 1 - (p - length) - 1, p))
-
-
-def cv_invert3(S):
-    """OpenCV's closed 3 x 3 inverse in double, in the operand order of csrc/xp_common.h: xp_cv_invert3."""
-    S = np.asarray(S, np.float64).reshape(9)
-    d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6])
-    if d == 0.0:
-        return np.zeros(9)
-    d = 1.0 / d
-    return np.array([(S[4] * S[8] - S[5] * S[7]) * d, (S[2] * S[7] - S[1] * S[8]) * d, (S[1] * S[5] - S[2] * S[4]) * d,
-                     (S[5] * S[6] - S[3] * S[8]) * d, (S[0] * S[8] - S[2] * S[6]) * d, (S[2] * S[3] - S[0] * S[5]) * d,
-                     (S[3] * S[7] - S[4] * S[6]) * d, (S[1] * S[6] - S[0] * S[7]) * d, (S[0] * S[4] - S[1] * S[3]) * d])
-
-
-def _fixed_point_source(Hm, h, w, scale):
-    """WarpPerspectiveInvoker's integer source coordinates of every destination pixel: scale = 32 (INTER_LINEAR, 1/32 pixel) or 1
-    (INTER_NEAREST).  The row base is formed at the first column of the pixel's block, the in-block offset added afterwards."""
-    m = cv_invert3(Hm)
-    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    bw = min(64, w) if h >= 16 else min(w, 1024 // h)
-    xb = (x // bw * bw).astype(np.float64)
-    x1 = x.astype(np.float64) - xb
-    y = y.astype(np.float64)
-    X0 = m[0] * xb + m[1] * y + m[2]
-    Y0 = m[3] * xb + m[4] * y + m[5]
-    W0 = m[6] * xb + m[7] * y + m[8]
-    W = W0 + m[6] * x1
-    with np.errstate(divide="ignore", invalid="ignore"):
-        W = np.where(W != 0.0, scale / W, 0.0)
-        fX = np.maximum(-2147483648.0, np.minimum(2147483647.0, (X0 + m[0] * x1) * W))
-        fY = np.maximum(-2147483648.0, np.minimum(2147483647.0, (Y0 + m[3] * x1) * W))
-    return np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)          # round half to even, as lrint
-
-
-def warp_perspective_f32(image, Hm, border_reflect):
-    """cv2.warpPerspective(image f32 (h, w), Hm, (w, h), INTER_LINEAR, BORDER_REFLECT_101 | BORDER_CONSTANT) in the f32 arithmetic of
-    csrc/warp.hip: returns f32, to be compared for equality."""
-    image = np.asarray(image, np.float32)
-    h, w = image.shape
-    X, Y = _fixed_point_source(Hm, h, w, 32.0)
-    sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
-    fx, fy = (X & 31).astype(np.float32) * np.float32(0.03125), (Y & 31).astype(np.float32) * np.float32(0.03125)
-    one = np.float32(1)
-
-    def tap(xx, yy):
-        if border_reflect:
-            return image[border_interpolate_101(yy, h), border_interpolate_101(xx, w)]
-        inside = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
-        return np.where(inside, image[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)], np.float32(0))
-
-    t0, t1, t2, t3 = tap(sx, sy), tap(sx + 1, sy), tap(sx, sy + 1), tap(sx + 1, sy + 1)
-    w0, w1, w2, w3 = (one - fy) * (one - fx), (one - fy) * fx, fy * (one - fx), fy * fx
-    out = ((t0 * w0 + t1 * w1) + t2 * w2) + t3 * w3
-    assert out.dtype == np.float32
-    return out
-
-
-def compute_valid_mask(shape, Hm, erosion_radius=0, mask_border=False):
-    """reference homographies.py: compute_valid_mask: the INTER_NEAREST warp of ones, then the (2r+1)^2 erosion behind a zero frame
-    (mask_border) or cv2.erode's default border, which never erodes."""
-    h, w = shape
-    X, Y = _fixed_point_source(Hm, h, w, 1.0)
-    mask = ((X >= 0) & (X < w) & (Y >= 0) & (Y < h)).astype(np.uint8)
-    r = int(erosion_radius)
-    if r > 0:
-        pad = np.full((h + 2 * r, w + 2 * r), 0 if mask_border else 1, np.uint8)
-        pad[r:r + h, r:r + w] = mask
-        out = np.ones((h, w), np.uint8)
-        for dy in range(2 * r + 1):
-            for dx in range(2 * r + 1):
-                out = np.minimum(out, pad[dy:dy + h, dx:dx + w])
-        mask = out
-    return mask.astype(bool)
 
 
 # ----------------------------------------------------------------------------------------------- labels

@@ -2,8 +2,9 @@
 OpenCV's documented INTER_LINEAR / BORDER_CONSTANT fixed-point scheme; PARITY UNPINNED vs OpenCV itself, which is absent from the reference tree and the
 image).  These pin the restatement to the closed-form cases the scheme must satisfy, independently of the HIP kernel it later checks."""
 import numpy as np
+import pytest
 
-from oracle import xpoint_oracle as xo
+from oracle import cv_restated, xpoint_oracle as xo
 
 
 def _img(h, w, seed=0):
@@ -70,3 +71,20 @@ def test_multichannel_dsize_and_quantisation_helper():
         assert np.array_equal(o[..., c], xo.warp_perspective(np.ascontiguousarray(rgb[..., c]), M, (50, 12)))
     g = np.array([[-0.5, 0.0, 0.5, 0.999, 1.0, 7.0]], dtype=np.float32)
     assert xo.to_u8_image(g).tolist() == [[0, 0, 127, 254, 255, 255]]
+
+
+@pytest.mark.parametrize("kind", ["projective", "strong"])
+@pytest.mark.parametrize("shape", [(24, 200), (9, 130), (3, 700), (16, 65), (15, 69), (40, 56), (1, 1)])
+def test_numpy_restatement_equals_the_c_oracle_bit_for_bit(shape, kind):
+    """The two CPU yardsticks of the kernels that share csrc/cv_geom.h agree: the numpy f32 warp with constant border
+    (oracle/cv_restated.py) against the plain-C oracle, on shapes that drive the block structure of the coordinate arithmetic (several
+    64-wide blocks with a ragged last one, heights under 16 where the block width follows the height, one pixel) and on matrices whose
+    horizon comes near (projective) or crosses (strong) the image: the W == 0, clamp and saturation paths."""
+    from tests.test_gpu_warp import _homography
+    h, w = shape
+    img = np.random.default_rng(h * 1000 + w).random((h, w), dtype=np.float32)
+    M = _homography(kind, h, w)
+    want = xo.warp_perspective(img, M)
+    got = cv_restated.warp_perspective_f32(img, M, False)
+    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), int((got.view(np.uint32) != want.view(np.uint32)).sum())

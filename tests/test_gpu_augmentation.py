@@ -101,6 +101,80 @@ def test_label_maps_equal_the_restatement_and_the_reference(gpu_lib, golden):
     assert np.array_equal(mask[0, 0].cpu().numpy(), A.compute_valid_mask(m.shape, Hm, 0, True))
 
 
+# Shapes (h, w) that drive the block structure of OpenCV's coordinate arithmetic (csrc/cv_geom.h): the row base is formed at the first
+# column of the pixel's block.  24 x 200: 64-wide blocks, three full plus a ragged 8; 16 x 65: ragged 1; 9 x 130: a height under 16, 113-wide
+# blocks, ragged 17; 3 x 700: 341-wide blocks, ragged 18; one pixel.  Matrices of tests/test_gpu_warp.py: the horizon comes near
+# (projective) or crosses (strong) the image, or the inverse is the zero matrix (singular): W == 0, the clamp and the 16-bit saturation.
+BLOCK_SHAPES = [(24, 200), (16, 65), (9, 130), (3, 700), (1, 1)]
+BLOCK_KINDS = ["projective", "strong", "singular"]
+_block_cache = {}
+
+
+def _block_case(shape):
+    """images, matrices and the restatement's results of one shape, computed once; no test writes to them"""
+    if shape not in _block_cache:
+        from tests.test_gpu_warp import _homography
+        h, w = shape
+        img = _images(len(BLOCK_KINDS), h, w, 100 * h + w)
+        Hs = np.stack([_homography(k, h, w) for k in BLOCK_KINDS])
+        case = {"img": img, "Hs": Hs}
+        for reflect in (True, False):
+            case[reflect] = np.stack([A.warp_perspective_f32(img[i, 0], Hs[i], reflect) for i in range(len(BLOCK_KINDS))])
+        for r, frame in ((0, True), (2, True), (2, False)):
+            case[r, frame] = np.stack([A.compute_valid_mask(shape, Hs[i], r, frame) for i in range(len(BLOCK_KINDS))])
+        _block_cache[shape] = case
+    return _block_cache[shape]
+
+
+def _assert_masks_are_not_trivial(shape, mask):
+    """where the restatement gives a mask that is neither empty nor full (fractions 0.81, 0.54, 0.54, 0.08 for projective, 0.20 for strong
+    at 24 x 200; the strong masks of the smaller shapes are empty or nearly so and are not asserted)"""
+    h, w = shape
+    if shape != (1, 1):
+        assert 0 < int(mask[BLOCK_KINDS.index("projective")].sum()) < h * w
+    if shape == (24, 200):
+        assert 0 < int(mask[BLOCK_KINDS.index("strong")].sum()) < h * w
+
+
+@pytest.mark.parametrize("border_reflect", [True, False])
+@pytest.mark.parametrize("shape", BLOCK_SHAPES)
+def test_warp_through_the_block_structure(gpu_lib, shape, border_reflect):
+    h, w = shape
+    case = _block_case(shape)
+    d = torch.from_numpy(case["img"]).to(DEV)
+    out, _, mask = aug.homographic_augmentation(d, None, case["Hs"], border_reflect=border_reflect)
+    got = out.cpu().numpy()
+    assert got.shape == case["img"].shape and got.dtype == np.float32
+    for i, kind in enumerate(BLOCK_KINDS):
+        assert np.array_equal(got[i, 0].view(np.uint32), case[border_reflect][i].view(np.uint32)), kind
+    assert np.array_equal(mask[:, 0].cpu().numpy(), case[0, True])
+    _assert_masks_are_not_trivial(shape, mask[:, 0].cpu().numpy())
+    if not border_reflect:
+        ref = utils.warp_perspective(d, case["Hs"])
+        assert ref.shape == out.shape and torch.equal(ref.contiguous().view(torch.int32), out.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("radius,mask_border", [(0, True), (2, True), (2, False)])
+@pytest.mark.parametrize("shape", BLOCK_SHAPES)
+def test_valid_mask_through_the_block_structure(gpu_lib, shape, radius, mask_border):
+    h, w = shape
+    case = _block_case(shape)
+    K = len(BLOCK_KINDS)
+    Hd = torch.from_numpy(case["Hs"].reshape(K, 9)).to(DEV)
+    direct, tmp = torch.empty((K, h, w), dtype=torch.uint8, device=DEV), torch.empty((K, h, w), dtype=torch.uint8, device=DEV)
+    _lib.call("xp_ha_valid_mask", _lib.ptr(Hd), _lib.ptr(direct), _lib.ptr(tmp), K, h, w, radius, 1 if mask_border else 0, _lib.current_stream())
+    torch.cuda.synchronize()
+    want = case[radius, mask_border]
+    for i, kind in enumerate(BLOCK_KINDS):
+        assert np.array_equal(direct[i].cpu().numpy().astype(bool), want[i]), kind
+    # the augmentation's mask is this entry point's (valid_border_margin = radius / 2)
+    _, _, mask = aug.homographic_augmentation(torch.from_numpy(case["img"]).to(DEV), None, case["Hs"], valid_border_margin=radius // 2,
+                                              mask_border=mask_border)
+    assert np.array_equal(mask[:, 0].cpu().numpy(), want)
+    if radius == 0:
+        _assert_masks_are_not_trivial(shape, want)
+
+
 # ----------------------------------------------------------------------------------------------- photometric
 def _run(img, prog, fields=None, seed=0, sample_ids=None):
     out = aug.photometric_augmentation(torch.from_numpy(img).to(DEV), prog, seed, sample_ids=sample_ids, fields=fields)

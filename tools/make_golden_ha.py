@@ -9,8 +9,8 @@ Two stand-ins are installed on top of the harness shims, both written from the d
     [0, 0, 1]]) and geometry.warp.homography_warper.homography_warp (grid = torch.linspace(-1, 1, .), the projective map with a plain
     division, then the REAL torch.nn.functional.grid_sample without align_corners, i.e. align_corners=False) -- so the sampling is
     pinned to torch itself;
-  * cv2: warpPerspective (INTER_NEAREST: OpenCV's documented scheme, inverse map, 64-wide block base, round half to even, 0 outside),
-    erode (square kernel, the default border never erodes) and getPerspectiveTransform (the 8 x 8 solve in float64).
+  * cv2: warpPerspective (INTER_NEAREST) and erode (square kernel, the default border never erodes) by OpenCV's documented scheme as
+    oracle/cv_restated.py restates it, and getPerspectiveTransform (the 8 x 8 solve in float64).
 sample_homography is wrapped only to RECORD the matrices it returns, compute_valid_mask to record the masks, and the nearest-mode warps
 (count_sample) to record the count maps.  One thread; the file is written with fixed zip timestamps, so a re-run is byte-identical.
 """
@@ -26,6 +26,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from oracle import cv_restated  # noqa: E402
 from oracle.refharness import build_ref, stubs  # noqa: E402
 from xpoint_amd import synth  # noqa: E402
 
@@ -65,53 +66,15 @@ def homography_warp(patch_src, dst_homo_src, dsize, mode='bilinear', padding_mod
 
 
 # ------------------------------------------------------------------------------------------------ cv2 stand-ins
-def _cv_invert3(S):
-    d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6])
-    if d == 0.0:
-        return np.zeros(9)
-    d = 1.0 / d
-    return np.array([(S[4] * S[8] - S[5] * S[7]) * d, (S[2] * S[7] - S[1] * S[8]) * d, (S[1] * S[5] - S[2] * S[4]) * d,
-                     (S[5] * S[6] - S[3] * S[8]) * d, (S[0] * S[8] - S[2] * S[6]) * d, (S[2] * S[3] - S[0] * S[5]) * d,
-                     (S[3] * S[7] - S[4] * S[6]) * d, (S[1] * S[6] - S[0] * S[7]) * d, (S[0] * S[4] - S[1] * S[3]) * d])
-
-
 def warp_perspective(src, M, dsize, flags=0):
     assert flags == 0, "stand-in: INTER_NEAREST only"
-    W, H = dsize
-    m = _cv_invert3(np.asarray(M, dtype=np.float64).reshape(-1))
-    src = np.asarray(src)
-    Hs, Ws = src.shape[:2]
-    bw = min(64, W) if H >= 16 else min(W, 1024 // H)
-    x = np.arange(W, dtype=np.float64)
-    xb = np.floor_divide(np.arange(W), bw) * bw
-    x1 = x - xb
-    out = np.zeros((H, W), dtype=src.dtype)
-    for y in range(H):
-        X0 = m[0] * xb + m[1] * y + m[2]
-        Y0 = m[3] * xb + m[4] * y + m[5]
-        W0 = m[6] * xb + m[7] * y + m[8]
-        Wv = W0 + m[6] * x1
-        with np.errstate(divide="ignore"):
-            Wv = np.where(Wv != 0.0, 1.0 / np.where(Wv != 0.0, Wv, 1.0), 0.0)
-        fX = np.clip((X0 + m[0] * x1) * Wv, -2147483648.0, 2147483647.0)
-        fY = np.clip((Y0 + m[3] * x1) * Wv, -2147483648.0, 2147483647.0)
-        X = np.rint(fX).astype(np.int64); Y = np.rint(fY).astype(np.int64)
-        ok = (X >= 0) & (X < Ws) & (Y >= 0) & (Y < Hs)
-        out[y, ok] = src[Y[ok], X[ok]]
-    return out
+    return cv_restated.warp_perspective_nearest(src, M, dsize[1], dsize[0])
 
 
 def erode(src, kernel, iterations=1):
-    assert iterations == 1
     kh, kw = np.asarray(kernel).shape
-    ry, rx = kh // 2, kw // 2
-    p = np.pad(np.asarray(src), ((ry, ry), (rx, rx)), constant_values=np.inf)
-    H, W = src.shape
-    out = np.full((H, W), np.inf)
-    for dy in range(kh):
-        for dx in range(kw):
-            out = np.minimum(out, p[dy:dy + H, dx:dx + W])
-    return out.astype(np.asarray(src).dtype)
+    assert iterations == 1 and kh == kw and kh % 2 == 1, "stand-in: one pass of an odd square kernel"
+    return cv_restated.erode(src, kh // 2)
 
 
 def get_perspective_transform(src, dst):

@@ -229,3 +229,19 @@ def current_stream(device=None):
     if device is not None and hasattr(device, "device"):
         device = device.device
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def matrix_table(matrices, count, device, who, broadcast=False):
+    """The contiguous (count, 9) float64 device table the warp kernels read, from 3 x 3 matrices given as numpy, a CPU tensor or a
+    device tensor (which makes no host round trip).  broadcast: a single matrix serves all `count` images.  `who` opens the error text."""
+    import numpy as np
+    import torch
+    if torch.is_tensor(matrices) and matrices.is_cuda:
+        t = matrices.to(torch.float64).reshape(-1, 9)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(matrices.cpu() if torch.is_tensor(matrices) else matrices, dtype=np.float64).reshape(-1, 9))).to(device)
+    if broadcast and t.shape[0] == 1 and count > 1:
+        t = t.expand(count, 9)
+    if t.shape[0] != count:
+        raise ValueError(f"{who}: {t.shape[0]} matrices for {count} images")
+    return t.contiguous()

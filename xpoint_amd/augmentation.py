@@ -47,17 +47,6 @@ def _need_device(t, what):
         raise _lib.XPointHipError(f"{what} needs device tensors: xpoint_amd has no CPU fallback")
 
 
-def _matrices(homographies, B, device):
-    if torch.is_tensor(homographies) and homographies.is_cuda:
-        Hd = homographies.to(torch.float64).reshape(-1, 9).contiguous()
-    else:
-        Hd = torch.from_numpy(np.ascontiguousarray(np.asarray(homographies.cpu() if torch.is_tensor(homographies) else homographies,
-                                                              dtype=np.float64).reshape(-1, 9))).to(device)
-    if Hd.shape[0] != B:
-        raise ValueError(f"{Hd.shape[0]} homographies for {B} images")
-    return Hd
-
-
 def homographic_augmentation(images, keypoint_maps, homographies, warp=None, border_reflect=True, valid_border_margin=0, mask_border=True):
     """The reference's homographic_augmentation for a batch, given the homographies.
 
@@ -77,7 +66,7 @@ def homographic_augmentation(images, keypoint_maps, homographies, warp=None, bor
     B, _, h, w = images.shape
     dev = images.device
     src = images.contiguous()
-    Hd = _matrices(homographies, B, dev)
+    Hd = _lib.matrix_table(homographies, B, dev, "homographic_augmentation")
     flags = None
     if warp is not None:
         flags = torch.as_tensor(warp).to(device=dev, dtype=torch.bool).reshape(-1).to(torch.uint8).contiguous()

@@ -14,8 +14,8 @@
 //                     The (w - 1) normalisation against align_corners = False sampling is the reference's half-pixel inconsistency,
 //                     kept on purpose.
 //   xp_ha_valid_mask  cv2.warpPerspective(ones, H, INTER_NEAREST) + cv2.erode((2r+1)^2) with the optional 1-pixel zero frame (mask_border):
-//                     OpenCV's documented nearest scheme (the 3 x 3 inverse and the 64-wide block base of csrc/warp.hip, 1 / W instead of
-//                     32 / W, round half to even, 0 outside), the erosion separable (row pass, column pass).  Parity with OpenCV unpinned.
+//                     OpenCV's documented nearest scheme (csrc/cv_geom.h at scale 1, 0 outside), the erosion separable (row pass, column pass).
+//                     Parity with OpenCV unpinned.
 //   xp_ha_gaussian    utils.get_gaussian_filter behind nn.ReflectionPad2d: depthwise k x k on (n, H, W).
 //   xp_ha_accumulate  per output pixel, the chunk's views IN ORDER: unwarp (bilinear, zeros) the forward outputs with the sampling matrix of
 //                     inverse(H), combine (prod / sum per tap before interpolating; window: search_window over the unwarped maps, a tile
@@ -24,7 +24,7 @@
 //                     original images) initialises the sums unmasked with count = 1.  finalize: divide, sqrt (prod) / * 0.5 (sum),
 //                     min_count.
 // All four are memory-bound (DESIGN.md "Homographic adaptation"): one thread per output pixel, consecutive lanes on consecutive pixels.
-#include "xp_common.h"
+#include "cv_geom.h"
 #include "../../include/xpoint_hip.h"
 
 namespace {
@@ -83,7 +83,7 @@ template <int BILINEAR, int REFLECT>
 __global__ __launch_bounds__(256) void ha_warp_kernel(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ M,
                                                       int n_src, int Hs, int Ws, int Hd, int Wd) {
     const int i = blockIdx.z;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = xp_tile_x(), y = xp_tile_y();
     if (x >= Wd || y >= Hd) return;
     const float* m = M + (size_t)(i / n_src) * 9;
     const float* s = src + (size_t)(i % n_src) * Hs * Ws;
@@ -106,25 +106,11 @@ __global__ __launch_bounds__(256) void ha_warp_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void ha_mask_warp_kernel(const double* __restrict__ Hm, uint8_t* __restrict__ out, int H, int W) {
     __shared__ double s_m[9];
     const int k = blockIdx.z;
-    if (threadIdx.x == 0) {
-        double t[9];
-        xp_cv_invert3(Hm + (size_t)k * 9, t);
-        for (int j = 0; j < 9; ++j) s_m[j] = t[j];
-    }
-    __syncthreads();
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    xp_cv_load_map(s_m, Hm + (size_t)k * 9, false, true);
+    const int x = xp_tile_x(), y = xp_tile_y();
     if (x >= W || y >= H) return;
-    const int bw0 = W < 64 ? W : 64;
-    const int bw = H >= 16 ? bw0 : (W < 1024 / H ? W : 1024 / H);
-    const int xb = x / bw * bw, x1 = x - xb;
-    const double X0 = s_m[0] * xb + s_m[1] * y + s_m[2];
-    const double Y0 = s_m[3] * xb + s_m[4] * y + s_m[5];
-    const double W0 = s_m[6] * xb + s_m[7] * y + s_m[8];
-    double Wv = W0 + s_m[6] * x1;
-    Wv = Wv != 0.0 ? 1.0 / Wv : 0.0;
-    const double fX = fmax(-2147483648.0, fmin(2147483647.0, (X0 + s_m[0] * x1) * Wv));
-    const double fY = fmax(-2147483648.0, fmin(2147483647.0, (Y0 + s_m[3] * x1) * Wv));
-    const int X = __double2int_rn(fX), Y = __double2int_rn(fY);
+    int X, Y;
+    xp_cv_source<1>(s_m, x, y, H, W, X, Y);
     out[((size_t)k * H + y) * W + x] = ((unsigned)X < (unsigned)W && (unsigned)Y < (unsigned)H) ? 1 : 0;
 }
 
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(256) void ha_mask_warp_kernel(const double* __restr
 template <int VERTICAL>
 __global__ __launch_bounds__(256) void ha_erode_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W, int r, int frame) {
     const int k = blockIdx.z;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = xp_tile_x(), y = xp_tile_y();
     if (x >= W || y >= H) return;
     const uint8_t* p = in + (size_t)k * H * W;
     int v = 1;
@@ -150,7 +136,7 @@ __device__ __forceinline__ int ha_reflect_index(int i, int n) { return i < 0 ? -
 __global__ __launch_bounds__(256) void ha_gaussian_kernel(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ w,
                                                           int H, int W, int ks) {
     const int i = blockIdx.z;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = xp_tile_x(), y = xp_tile_y();
     if (x >= W || y >= H) return;
     const float* p = src + (size_t)i * H * W;
     const int r = ks / 2;
@@ -282,7 +268,7 @@ extern "C" int xp_ha_warp(const float* src, float* dst, const float* M, int n_sr
     XP_CHECK_ARG(mode == XP_HA_NEAREST || mode == XP_HA_BILINEAR, "xp_ha_warp: unknown mode %d", mode);
     XP_CHECK_ARG(padding == XP_HA_ZEROS || padding == XP_HA_REFLECTION, "xp_ha_warp: unknown padding %d", padding);
     XP_CHECK_ARG(src != dst, "xp_ha_warp: in-place warp is not supported");
-    const dim3 grid(xp_cdiv(Wd, 64), xp_cdiv(Hd, 4), n_dst), block(256);
+    const dim3 grid = xp_tile_grid(Wd, Hd, n_dst), block(256);
     XpProfScope prof("ha_warp", (hipStream_t)stream, 0.0, 8.0 * n_dst * Hd * Wd);
     const bool bil = mode == XP_HA_BILINEAR, refl = padding == XP_HA_REFLECTION;
     if (bil && refl) hipLaunchKernelGGL((ha_warp_kernel<1, 1>), grid, block, 0, (hipStream_t)stream, src, dst, M, n_src, Hs, Ws, Hd, Wd);
@@ -298,7 +284,7 @@ extern "C" int xp_ha_valid_mask(const double* Hm, uint8_t* mask, uint8_t* tmp, i
     XP_CHECK_ARG(K > 0 && K <= 65535 && H > 0 && W > 0 && H < 32768 && W < 32768, "xp_ha_valid_mask: bad shape (%d masks of %d x %d)", K, H, W);
     XP_CHECK_ARG(erosion_radius >= 0 && erosion_radius < 4096, "xp_ha_valid_mask: bad erosion radius %d", erosion_radius);
     XP_CHECK_ARG(((uintptr_t)Hm & 7) == 0, "xp_ha_valid_mask: misaligned matrix pointer");
-    const dim3 grid(xp_cdiv(W, 64), xp_cdiv(H, 4), K), block(256);
+    const dim3 grid = xp_tile_grid(W, H, K), block(256);
     XpProfScope prof("ha_valid_mask", (hipStream_t)stream, 0.0, (erosion_radius > 0 ? 5.0 : 1.0) * K * H * W);
     hipLaunchKernelGGL(ha_mask_warp_kernel, grid, block, 0, (hipStream_t)stream, Hm, mask, H, W);
     if (erosion_radius > 0) {
@@ -315,7 +301,7 @@ extern "C" int xp_ha_gaussian(const float* src, float* dst, const float* weights
     XP_CHECK_ARG(n > 0 && n <= 65535 && H > 0 && W > 0 && H <= 4 * 65535, "xp_ha_gaussian: bad shape (%d x %d x %d)", n, H, W);
     XP_CHECK_ARG(ksize >= 1 && ksize % 2 == 1 && ksize / 2 < H && ksize / 2 < W, "xp_ha_gaussian: ksize %d must be odd with a reflection pad smaller than the image", ksize);
     XP_CHECK_ARG(src != dst, "xp_ha_gaussian: in-place filtering is not supported");
-    const dim3 grid(xp_cdiv(W, 64), xp_cdiv(H, 4), n), block(256);
+    const dim3 grid = xp_tile_grid(W, H, n), block(256);
     XpProfScope prof("ha_gaussian", (hipStream_t)stream, 2.0 * ksize * ksize * n * H * W, 8.0 * n * H * W);
     hipLaunchKernelGGL(ha_gaussian_kernel, grid, block, 0, (hipStream_t)stream, src, dst, weights, H, W, ksize);
     XP_LAUNCH_CHECK();

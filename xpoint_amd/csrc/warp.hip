@@ -3,25 +3,15 @@
 // (predict_align_image_pair.py:308; demo.py:225-249), i.e. flags = INTER_LINEAR, borderValue = 0, M = the FORWARD map src -> dst, which
 // OpenCV inverts before the per-pixel inverse mapping.  SURVEY.md 8(f) rank 2.
 //
-// OpenCV is absent from /root/reference and from this image, so the arithmetic below is the DOCUMENTED scheme of OpenCV's
-// imgproc (warpPerspective -> remap, INTER_BITS = 5, INTER_REMAP_COEF_BITS = 15) restated from its published source — "parity unpinned"
-// (DESIGN.md section 4); the oracle (oracle/csrc/oracle_kernels.c: xo_warp_perspective_*) states the same scheme in plain C and the GPU
-// tests demand bit-equality with it.
-//   1. M^-1 by the closed 3x3 cofactor form in double (no LU): t = adj(M) * (1 / det), det == 0 -> the zero matrix.
-//   2. per destination pixel (x, y), in double, with the block structure of OpenCV's WarpPerspectiveInvoker (the row base is formed at
-//      the first column xb of the pixel's 64-wide block, the in-block offset x1 added afterwards):
-//          X0 = m0 * xb + m1 * y + m2,  Y0 = m3 * xb + m4 * y + m5,  W0 = m6 * xb + m7 * y + m8
-//          W = W0 + m6 * x1;  W = W ? 32 / W : 0
-//          fX = clamp((X0 + m0 * x1) * W, INT_MIN, INT_MAX),  fY likewise;   X = lrint(fX), Y = lrint(fY)        (round half to even)
-//          sx = sat16(X >> 5), sy = sat16(Y >> 5),  ax = X & 31, ay = Y & 31
-//   3. bilinear taps at (sx, sy), (sx + 1, sy), (sx, sy + 1), (sx + 1, sy + 1); a tap outside the source reads the border value 0.
+// The coordinate arithmetic (the 3 x 3 inverse in double, the block-structured row base, the 1/32-pixel fixed point, the f32 bilinear combine)
+// is OpenCV's documented scheme, stated once in csrc/cv_geom.h ("parity unpinned"); the oracle
+// (oracle/csrc/oracle_kernels.c: xo_warp_perspective_*) states the same scheme in plain C and the GPU tests demand bit-equality with it.
+// This file adds the taps (a tap outside the source reads the border value 0) and the u8 path:
 //        u8 : weights w = 32768 * (1 - ay / 32 | ay / 32) * (1 - ax / 32 | ax / 32) = exact integers (32 - ay | ay) * (32 - ax | ax) * 32,
 //             out = (sum w_i * tap_i + 16384) >> 15
-//        f32: weights (1 - fy) * (1 - fx), (1 - fy) * fx, fy * (1 - fx), fy * fx with fx = ax / 32 (exact in f32),
-//             out = ((t0 * w0 + t1 * w1) + t2 * w2) + t3 * w3      (separate multiplies and adds, left to right; built with -ffp-contract=off)
 // One thread per destination pixel (all channels), 64 x 4 pixels per workgroup: consecutive lanes write consecutive pixels; the four taps of
 // neighbouring pixels share cache lines.  HBM-bound: a 480 x 640 u8 image is 0.3 MB in, 0.3 MB out.
-#include "xp_common.h"
+#include "cv_geom.h"
 #include "../../include/xpoint_hip.h"
 
 namespace {
@@ -31,8 +21,6 @@ struct WarpParams {
     const uint8_t* mask;                                    // MODE 2 only, may be null: (batch, Hs, Ws) valid mask, nonzero = valid
     int Hs, Ws, Hd, Wd, C, Cd, inverse_map;
 };
-
-__device__ __forceinline__ int warp_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 // source element (channel c) at (sx, sy), 0 outside.  MODE 0: u8 source; 1: f32 source; 2: f32 source quantised on load as the reference
 // does before warping: (np.clip(img, 0, 1) * 255.0).astype(np.uint8)  (predict_align_image_pair.py:271: f32 multiply, truncation), after
@@ -58,27 +46,12 @@ template <int MODE>
 __global__ __launch_bounds__(256) void warp_perspective_kernel(WarpParams p) {
     __shared__ double s_m[9];
     const int b = blockIdx.z;
-    if (threadIdx.x == 0) {
-        const double* S = p.M + (size_t)b * 9;
-        double t[9];
-        if (p.inverse_map) { for (int k = 0; k < 9; ++k) t[k] = S[k]; } else xp_cv_invert3(S, t);
-        for (int k = 0; k < 9; ++k) s_m[k] = t[k];
-    }
-    __syncthreads();
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    xp_cv_load_map(s_m, p.M + (size_t)b * 9, p.inverse_map, true);
+    const int x = xp_tile_x(), y = xp_tile_y();
     if (x >= p.Wd || y >= p.Hd) return;
-    const int bw0 = p.Wd < 64 ? p.Wd : 64;                 // OpenCV's block width: min(BLOCK_SZ * BLOCK_SZ / min(BLOCK_SZ / 2, height), width) = min(64, width) for height >= 16
-    const int bw = p.Hd >= 16 ? bw0 : (p.Wd < 1024 / p.Hd ? p.Wd : 1024 / p.Hd);
-    const int xb = x / bw * bw, x1 = x - xb;
-    const double X0 = s_m[0] * xb + s_m[1] * y + s_m[2];
-    const double Y0 = s_m[3] * xb + s_m[4] * y + s_m[5];
-    const double W0 = s_m[6] * xb + s_m[7] * y + s_m[8];
-    double W = W0 + s_m[6] * x1;
-    W = W != 0.0 ? 32.0 / W : 0.0;
-    const double fX = fmax(-2147483648.0, fmin(2147483647.0, (X0 + s_m[0] * x1) * W));
-    const double fY = fmax(-2147483648.0, fmin(2147483647.0, (Y0 + s_m[3] * x1) * W));
-    const int X = __double2int_rn(fX), Y = __double2int_rn(fY);         // NaN (0 * inf) -> 0, as lrint's result is then unspecified in C
-    const int sx = warp_sat16(X >> 5), sy = warp_sat16(Y >> 5), ax = X & 31, ay = Y & 31;
+    int X, Y, sx, sy, ax, ay;
+    xp_cv_source<32>(s_m, x, y, p.Hd, p.Wd, X, Y);
+    xp_cv_split(X, sx, ax); xp_cv_split(Y, sy, ay);
     const size_t src_off = (size_t)b * p.Hs * p.Ws * p.C;
     const size_t dst_off = (((size_t)b * p.Hd + y) * p.Wd + x) * p.Cd;
     const void* src = MODE == 0 ? (const void*)(reinterpret_cast<const uint8_t*>(p.src) + src_off) : (const void*)(reinterpret_cast<const float*>(p.src) + src_off);
@@ -88,9 +61,7 @@ __global__ __launch_bounds__(256) void warp_perspective_kernel(WarpParams p) {
         const auto t0 = warp_tap<MODE>(src, mask, p.Hs, p.Ws, p.C, sx, sy, cs), t1 = warp_tap<MODE>(src, mask, p.Hs, p.Ws, p.C, sx + 1, sy, cs);
         const auto t2 = warp_tap<MODE>(src, mask, p.Hs, p.Ws, p.C, sx, sy + 1, cs), t3 = warp_tap<MODE>(src, mask, p.Hs, p.Ws, p.C, sx + 1, sy + 1, cs);
         if constexpr (MODE == 1) {
-            const float fx = (float)ax * 0.03125f, fy = (float)ay * 0.03125f;
-            const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;
-            reinterpret_cast<float*>(p.dst)[dst_off + c] = ((t0 * w0 + t1 * w1) + t2 * w2) + t3 * w3;
+            reinterpret_cast<float*>(p.dst)[dst_off + c] = xp_cv_bilinear_f32(t0, t1, t2, t3, ax, ay);
         } else {
             const int w0 = (32 - ay) * (32 - ax) * 32, w1 = (32 - ay) * ax * 32, w2 = ay * (32 - ax) * 32, w3 = ay * ax * 32;
             const int v = (t0 * w0 + t1 * w1 + t2 * w2 + t3 * w3 + 16384) >> 15;
@@ -115,7 +86,7 @@ extern "C" int xp_warp_perspective_masked(const void* src, const uint8_t* mask, 
                  "xp_warp_perspective: misaligned pointer");
     XP_CHECK_ARG(src != dst, "xp_warp_perspective: in-place warp is not supported");
     WarpParams p{src, dst, M, mask, Hs, Ws, Hd, Wd, channels, dst_channels, inverse_map ? 1 : 0};
-    const dim3 grid(xp_cdiv(Wd, 64), xp_cdiv(Hd, 4), batch), block(256);
+    const dim3 grid = xp_tile_grid(Wd, Hd, batch), block(256);
     const double px = (double)batch * Hd * Wd, eb = dtype == XP_WARP_F32 ? 4.0 : 1.0;
     XpProfScope prof("warp_perspective", (hipStream_t)stream, 0.0, px * dst_channels * eb + (double)batch * Hs * Ws * channels * (dtype == XP_WARP_U8 ? 1.0 : 4.0));
     if (dtype == XP_WARP_U8) hipLaunchKernelGGL(warp_perspective_kernel<0>, grid, block, 0, (hipStream_t)stream, p);

@@ -70,26 +70,6 @@ struct XpPerDeviceOnce {
     }
 };
 
-// OpenCV cv::invert of a 3 x 3 double matrix (DECOMP_LU): det3 and the cofactors in this operand order; a singular matrix gives zeros.
-// The inverse map of the warps in warp.hip and homadapt.hip.
-__device__ __forceinline__ void xp_cv_invert3(const double* __restrict__ S, double (&t)[9]) {
-    double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-    if (d != 0.0) {
-        d = 1.0 / d;
-        t[0] = (S[4] * S[8] - S[5] * S[7]) * d;
-        t[1] = (S[2] * S[7] - S[1] * S[8]) * d;
-        t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-        t[3] = (S[5] * S[6] - S[3] * S[8]) * d;
-        t[4] = (S[0] * S[8] - S[2] * S[6]) * d;
-        t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-        t[6] = (S[3] * S[7] - S[4] * S[6]) * d;
-        t[7] = (S[1] * S[6] - S[0] * S[7]) * d;
-        t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
-    } else {
-        for (int k = 0; k < 9; ++k) t[k] = 0.0;
-    }
-}
-
 static inline int xp_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Sticky status bits of xp_xpoint_forward_ex (include/xpoint_hip.h): OR-ed into the caller's device word by the kernels that produce

@@ -235,7 +235,8 @@ def _run(images, flags, net, config, mode, homographies, chunk):
     if hs:
         masks = torch.empty((len(hs), H, W), dtype=torch.uint8, device=dev)
         tmp = torch.empty_like(masks) if config['erosion_radius'] > 0 else None
-        _lib.check(lib.xp_ha_valid_mask(ptr(torch.from_numpy(np.stack(hs)).to(dev)), ptr(masks), ptr(tmp), len(hs), H, W,
+        Hd = _lib.matrix_table(np.stack(hs), len(hs), dev, "homographic_adaptation")
+        _lib.check(lib.xp_ha_valid_mask(ptr(Hd), ptr(masks), ptr(tmp), len(hs), H, W,
                                         int(config['erosion_radius']), int(bool(config['mask_border'])), st), "xp_ha_valid_mask")
     fs = int(config['filter_size'])
     gw = _gaussian_weights(fs).to(dev) if fs > 0 else None

@@ -324,7 +324,6 @@ def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, d
     tensor of B x H x W elements (nonzero = valid); the image is multiplied by it before the quantisation, as the reference's
     `optical *= mask_optical` (predict_align_image_pair.py:267) — the image itself is not modified.  Returns a device tensor shaped like the input with (Hd, Wd).
     Arithmetic: OpenCV's documented 1/32-pixel fixed-point scheme (include/xpoint_hip.h: xp_warp_perspective; parity unpinned)."""
-    import numpy as np
     if not (torch.is_tensor(img) and img.is_cuda):
         raise _lib.XPointHipError("warp_perspective needs a device tensor: xpoint_amd has no CPU fallback")
     if img.dtype not in (torch.uint8, torch.float32):
@@ -349,15 +348,7 @@ def warp_perspective(img, M, dsize=None, inverse_map=False, quantise_u8=False, d
     B, Hs, Ws, C = x.shape
     Wd, Hd = (Ws, Hs) if dsize is None else (int(dsize[0]), int(dsize[1]))
     Cd = C if dst_channels is None else int(dst_channels)
-    if torch.is_tensor(M) and M.is_cuda:
-        Md = M.to(torch.float64).reshape(-1, 9)
-    else:
-        Md = torch.from_numpy(np.ascontiguousarray(np.asarray(M.cpu() if torch.is_tensor(M) else M, dtype=np.float64).reshape(-1, 9))).to(x.device)
-    if Md.shape[0] == 1 and B > 1:
-        Md = Md.expand(B, 9)
-    if Md.shape[0] != B:
-        raise ValueError(f"warp_perspective: {Md.shape[0]} matrices for {B} images")
-    Md = Md.contiguous()
+    Md = _lib.matrix_table(M, B, x.device, "warp_perspective", broadcast=True)
     u8_out = x.dtype == torch.uint8 or quantise_u8
     out = torch.empty((B, Hd, Wd, Cd), dtype=torch.uint8 if u8_out else torch.float32, device=x.device)
     dtype = 0 if x.dtype == torch.uint8 else (2 if quantise_u8 else 1)
