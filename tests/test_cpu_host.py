@@ -1,6 +1,6 @@
 """CPU (-m "not gpu"): the C-ABI library loads and exports every symbol include/xpoint_hip.h declares, and the
 host-side logic that needs no GPU (context / parameter layout / weight packing / config and error behaviour)
-is correct.  No compute entry point is called here."""
+is correct.  No compute entry point is called here with arguments that pass its checks."""
 import ctypes
 import os
 
@@ -371,3 +371,89 @@ def test_arithmetic_switch_scope_restores_what_it_found():
     finally:
         _lib.call("xp_set_dense_products", before[0]); _lib.call("xp_set_dense_engine", before[1]); _lib.call("xp_set_dense_override", before[3])
     assert get() == before
+
+
+# ------------------------------------------------------------------------------------------------ dense entry points: argument errors
+_P, _Q = 0x1000, 0x1008          # placeholder pointers: 16-byte aligned / 8 bytes off.  Never dereferenced: every case fails a check before any launch
+
+
+def _gemm_args(f16, **kw):
+    a = dict(A=_P, W=_P, C=_P, c_f32=0, bias=None, scale=None, shift=None, res=None, M=2, N=5, K=16, lda=16, ldc=5, ldres=5, act=0)
+    a.update(kw)
+    head = [a["A"], a["W"], a["C"]] + ([a["c_f32"]] if f16 else [])
+    return head + [a[k] for k in ("bias", "scale", "shift", "res", "M", "N", "K", "lda", "ldc", "ldres", "act")] + [None]
+
+
+def _conv_args(f16, **kw):
+    a = dict(x=_P, W=_P, y=_P, y_f32=0, bias=None, scale=None, shift=None, batch=1, Hi=4, Wi=6, Ci=8, Co=5, stride=1, reflect=0, act=0)
+    a.update(kw)
+    head = [a["x"], a["W"], a["y"]] + ([a["y_f32"]] if f16 else [])
+    return head + [a[k] for k in ("bias", "scale", "shift", "batch", "Hi", "Wi", "Ci", "Co", "stride", "reflect", "act")] + [None]
+
+
+# one row per check, in the order the entry point performs them: (what differs from a valid call, the text after "<entry>: ")
+_GEMM_F32_ERRORS = [
+    (dict(A=None), "null pointer"),
+    (dict(W=None), "null pointer"),
+    (dict(C=None), "null pointer"),
+    (dict(M=0), "bad shape 0 5 16"),
+    (dict(N=-1), "bad shape 2 -1 16"),
+    (dict(K=6, lda=8), "K and lda must be multiples of 4 (got 6, 8)"),
+    (dict(lda=18), "K and lda must be multiples of 4 (got 16, 18)"),
+    (dict(scale=_P), "scale and shift go together"),
+    (dict(shift=_P), "scale and shift go together"),
+    (dict(act=4), "bad act 4"),
+    (dict(act=-1), "bad act -1"),
+]
+_GEMM_F16_ERRORS = [
+    (dict(A=None), "null pointer"),
+    (dict(M=0), "bad shape 0 5 16"),
+    (dict(K=12, lda=16), "K and lda must be multiples of 8 halves (got 12, 16)"),
+    (dict(lda=20), "K and lda must be multiples of 8 halves (got 16, 20)"),
+    (dict(A=_Q), "A and W must be 16-byte aligned"),
+    (dict(W=_Q), "A and W must be 16-byte aligned"),
+    (dict(scale=_P), "scale and shift go together"),
+    (dict(act=4), "bad act 4"),
+    (dict(C=_Q), "C and res must be 16-byte aligned"),
+    (dict(res=_Q), "C and res must be 16-byte aligned"),
+]
+_CONV_F32_ERRORS = [
+    (dict(x=None), "null pointer"),
+    (dict(W=None), "null pointer"),
+    (dict(y=None), "null pointer"),
+    (dict(Ci=6), "Ci must be a multiple of 4 (got 6)"),
+    (dict(stride=3), "stride 1 or 2"),
+    (dict(stride=0), "stride 1 or 2"),
+    (dict(scale=_P), "scale and shift go together"),
+    (dict(shift=_P), "scale and shift go together"),
+    (dict(reflect=1, Hi=1), "reflection pad needs H,W >= 2"),
+    (dict(reflect=1, Wi=1), "reflection pad needs H,W >= 2"),
+]
+_CONV_F16_ERRORS = [
+    (dict(x=None), "null pointer"),
+    (dict(Ci=12), "Ci must be a multiple of 8 (got 12)"),
+    (dict(stride=3), "stride 1 or 2"),
+    (dict(scale=_P), "scale and shift go together"),
+    (dict(reflect=1, Hi=1), "reflection pad needs H,W >= 2"),
+    (dict(x=_Q), "buffers must be 16-byte aligned"),
+    (dict(W=_Q), "buffers must be 16-byte aligned"),
+    (dict(y=_Q), "buffers must be 16-byte aligned"),
+    (dict(Ci=7280), "Ci too large"),              # 9 * 7280 + 64 = 65584
+]
+_DENSE_ERROR_CASES = [(entry, _gemm_args, False, _GEMM_F32_ERRORS) for entry in ("xp_gemm_nt", "xp_gemm_nt_x3", "xp_gemm_nt_h2")] + \
+                     [("xp_gemm_nt_f16", _gemm_args, True, _GEMM_F16_ERRORS)] + \
+                     [(entry, _conv_args, False, _CONV_F32_ERRORS) for entry in ("xp_conv3x3_nhwc", "xp_conv3x3_nhwc_x3", "xp_conv3x3_nhwc_h2")] + \
+                     [("xp_conv3x3_nhwc_f16", _conv_args, True, _CONV_F16_ERRORS)]
+
+
+@pytest.mark.parametrize("entry,make,f16,table", _DENSE_ERROR_CASES, ids=[c[0] for c in _DENSE_ERROR_CASES])
+def test_dense_entry_argument_error_texts(entry, make, f16, table):
+    """Every argument check of the eight dense entry points, one call per check and each call tripping that check alone: XP_ERR_ARG and the whole
+    xp_last_error() text.  The pointers are placeholders, so the test needs every case to fail before a launch and does not run where a GPU is visible
+    (the texts do not depend on the device)."""
+    if torch.cuda.is_available():
+        pytest.skip("placeholder pointers: only where no launch can happen")
+    lib = _lib.load()
+    for change, text in table:
+        rc = getattr(lib, entry)(*make(f16, **change))
+        assert rc == -1 and lib.xp_last_error().decode() == f"{entry}: {text}", (entry, change, rc, lib.xp_last_error())

@@ -106,6 +106,112 @@ def _tags(fn):
     return out
 
 
+def _shape_tag_probe():
+    """Child of test_shape_tags_and_roofline_numerators (XP_PROF_SHAPES is read once per process): one launch per dense launcher with profiling on;
+    prints {tag: [launches, flops, bytes]} as one JSON line."""
+    import json
+    L = _lib()
+    lib = L.load()
+    st = L.current_stream()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(99)
+
+    def packs(W0, N, K):
+        out = []
+        for kind in ("x3", "h2"):
+            buf = torch.empty(getattr(lib, f"xp_split_weights_{kind}_bytes")(N, K), dtype=torch.uint8, device="cuda")
+            L.call(f"xp_split_weights_{kind}", L.ptr(W0), ctypes.c_void_p(buf.data_ptr()), N, K, st)
+            out.append(ctypes.c_void_p(buf.data_ptr()))
+            keep.append(buf)
+        return out
+
+    keep = []
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    # (a) plain GEMM with a residual and GELU
+    M, N, K = 130, 40, 32
+    A, W, R, C = _rand(g, (M, K)), _rand(g, (N, K)), _rand(g, (M, N)), torch.empty((M, N), device="cuda")
+    Wx3, Wh2 = packs(W, N, K)
+    Ah, Wh, Rh, Ch = A.half(), W.half(), R.half(), torch.empty((M, N), dtype=torch.float16, device="cuda")
+    # (b) strided 3 x 3 convolution: Ho 3, Wo 5, M 15, K 72
+    Hi, Wi, Ci, Co = 6, 10, 8, 40
+    X, Wc, Y = _rand(g, (Hi * Wi, Ci)), _rand(g, (Co, 9 * Ci)), torch.empty((15, Co), device="cuda")
+    Wcx3, Wch2 = packs(Wc, Co, 9 * Ci)
+    Xh, Wch, Yh = X.half(), Wc.half(), torch.empty((15, Co), dtype=torch.float16, device="cuda")
+    # (c) the ping-pong kernel, (d) the ring engine on a P32 image
+    Ac, Wcc, Cc = _rand(g, (130, 768)), _rand(g, (384, 768)), torch.empty((130, 384), device="cuda")
+    _, Wcch2 = packs(Wcc, 384, 768)
+    Ad, Wd, Cd = _rand(g, (130, 256)), _rand(g, (256, 256)), torch.empty((130, 256), device="cuda")
+    _, Wdh2 = packs(Wd, 256, 256)
+    Adp = torch.empty((130, 256), device="cuda")
+    L.call("xp_split_activations_h2", L.ptr(Ad), L.ptr(Adp), 130, 256, 256, st)
+
+    def run():
+        L.call("xp_gemm_nt", L.ptr(A), L.ptr(W), L.ptr(C), None, None, None, L.ptr(R), M, N, K, K, N, N, 1, st)
+        L.call("xp_conv3x3_nhwc", L.ptr(X), L.ptr(Wc), L.ptr(Y), None, None, None, 1, Hi, Wi, Ci, Co, 2, 0, 0, st)
+        for products in (6, 3):
+            _dense_products(products)
+            L.call("xp_gemm_nt_x3", L.ptr(A), Wx3, L.ptr(C), None, None, None, L.ptr(R), M, N, K, K, N, N, 1, st)
+            L.call("xp_conv3x3_nhwc_x3", L.ptr(X), Wcx3, L.ptr(Y), None, None, None, 1, Hi, Wi, Ci, Co, 2, 0, 0, st)
+        _dense_products(6)
+        L.call("xp_gemm_nt_h2", L.ptr(A), Wh2, L.ptr(C), None, None, None, L.ptr(R), M, N, K, K, N, N, 1, st)
+        L.call("xp_conv3x3_nhwc_h2", L.ptr(X), Wch2, L.ptr(Y), None, None, None, 1, Hi, Wi, Ci, Co, 2, 0, 0, st)
+        L.call("xp_gemm_nt_f16", vp(Ah), vp(Wh), vp(Ch), 0, None, None, None, vp(Rh), M, N, K, K, N, N, 1, st)
+        L.call("xp_conv3x3_nhwc_f16", vp(Xh), vp(Wch), vp(Yh), 0, None, None, None, 1, Hi, Wi, Ci, Co, 2, 0, 0, st)
+        L.call("xp_gemm_nt_h2", L.ptr(Ac), Wcch2, L.ptr(Cc), None, None, None, None, 130, 384, 768, 768, 384, 0, 0, st)
+        L.call("xp_gemm_nt_h2s", L.ptr(Adp), Wdh2, L.ptr(Cd), 0, None, None, None, None, 130, 256, 256, 256, 0, 0, st)
+
+    torch.cuda.synchronize()
+    L.call("xp_prof_reset")
+    L.call("xp_prof_enable", 1)
+    try:
+        run()
+        torch.cuda.synchronize()
+        out = {}
+        name = ctypes.create_string_buffer(96)
+        ms, cnt, fl, by = ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        for i in range(lib.xp_prof_count()):
+            lib.xp_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by))
+            out[name.value.decode()] = [cnt.value, fl.value, by.value]
+    finally:
+        L.call("xp_prof_enable", 0)
+        L.call("xp_prof_reset")
+    print("SHAPE_TAGS " + json.dumps(out, sort_keys=True))
+
+
+# what _shape_tag_probe printed on the commit before the dense engines' host code moved into csrc/dense_host.h: the tags are strings and the numerators
+# doubles formed from the same integer expressions, so equality is exact
+SHAPE_TAGS = {
+    "conv3x3_f16_mfma_128x64_M15_N40_K72": [1, 86400.0, 7920.0],
+    "conv3x3_f32_mfma_128x64_M15_N40_K72": [1, 86400.0, 15840.0],
+    "conv3x3_h2r_mfma_128x64_M15_N40_K72": [1, 86400.0, 15840.0],
+    "conv3x3_x3_mfma_128x64_M15_N40_K72": [1, 86400.0, 21600.0],
+    "conv3x3_x3_mfma_128x64_np3_M15_N40_K72": [1, 86400.0, 21600.0],
+    "gemm_f16_mfma_128x64_k32_M130_N40_K32": [1, 332800.0, 31680.0],
+    "gemm_f32_mfma_128x64_M130_N40_K32_gelu": [1, 332800.0, 63360.0],
+    "gemm_h2_mfma_128x64_M130_N40_K32_gelu": [1, 332800.0, 63360.0],
+    "gemm_h2p_mfma_128x128_M130_N384_K768": [1, 76677120.0, 1778688.0],
+    "gemm_ring_h2s_128x128_M130_N256_K256": [1, 17039360.0, 528384.0],
+    "gemm_x3_mfma_128x64_M130_N40_K32_gelu": [1, 332800.0, 65920.0],
+    "gemm_x3_mfma_128x64_np3_M130_N40_K32_gelu": [1, 332800.0, 65920.0],
+}
+
+
+def test_shape_tags_and_roofline_numerators(gpu_lib):
+    """Per-shape tags (XP_PROF_SHAPES=1) and the flops / bytes every dense launcher hands to the profiler, one case per launcher, against the recorded table."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", "import tests.test_gpu_batch_invariance as t; t._shape_tag_probe()"], env=dict(os.environ, XP_PROF_SHAPES="1"),
+                       capture_output=True, text=True, timeout=120, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("SHAPE_TAGS ")][-1]
+    got = json.loads(line[len("SHAPE_TAGS "):])
+    print(line)
+    assert got == SHAPE_TAGS
+
+
 def _report(entry, cls, layer, M, Mp, tm, tmp, equal, errs):
     e = " ".join(f"{err:.2e}/{bound:.2e}" for err, bound in errs)
     print(f"{entry:22s} {cls:4s} {str(layer):26s} M {M:6d} M' {Mp:6d}  {tm}  |  {tmp}  bits-equal {equal}  err/bound {e}")

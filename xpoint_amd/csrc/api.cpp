@@ -90,6 +90,12 @@ XpProfScope::~XpProfScope() {
     if (index_ < g_pending.size()) (void)hipEventRecord(g_pending[index_].e1, stream_);
 }
 
+// XP_PROF_SHAPES=1: per-shape tags (read once per process)
+bool xp_prof_by_shape() {
+    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
+    return by_shape;
+}
+
 extern "C" int xp_prof_enable(int on) { std::lock_guard<std::mutex> lk(g_pm); g_prof_on = on != 0; return XP_OK; }
 extern "C" int xp_prof_filter(const char* tag) { std::lock_guard<std::mutex> lk(g_pm); g_prof_filter = tag ? tag : ""; return XP_OK; }
 extern "C" int xp_prof_reset(void) { std::lock_guard<std::mutex> lk(g_pm); collect_locked(); g_acc.clear(); return XP_OK; }

@@ -491,8 +491,7 @@ static int layernorm_impl(const float* x, float* y, const float* w, const float*
     XP_CHECK_ARG(x && y && w && b, "xp_layernorm: null pointer");
     XP_CHECK_ARG(C > 0 && C <= 1024, "xp_layernorm: C must be in [1,1024] (got %d)", C);
     if (rows == 0) return XP_OK;
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    XpProfScope prof(by_shape ? ("layernorm_C" + std::to_string(C)).c_str() : "layernorm", (hipStream_t)stream, 8.0 * rows * C, 8.0 * rows * C);
+    XpProfScope prof(xp_prof_by_shape() ? ("layernorm_C" + std::to_string(C)).c_str() : "layernorm", (hipStream_t)stream, 8.0 * rows * C, 8.0 * rows * C);
     hipStream_t s = (hipStream_t)stream;
     const bool vec = (C % 4 == 0) && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)b) & 15) == 0);
     const int C4 = C / 4;

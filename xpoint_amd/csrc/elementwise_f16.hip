@@ -245,8 +245,7 @@ extern "C" int xp_layernorm_f16(const void* x, void* y, const float* w, const fl
     XP_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1024, "xp_layernorm_f16: C must be a multiple of 8 in [8, 1024] (got %d)", C);
     XP_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)b) & 15) == 0, "xp_layernorm_f16: buffers must be 16-byte aligned");
     if (rows == 0) return XP_OK;
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    XpProfScope prof(by_shape ? ("layernorm_f16_C" + std::to_string(C)).c_str() : "layernorm_f16", (hipStream_t)stream, 8.0 * rows * C, 4.0 * rows * C);
+    XpProfScope prof(xp_prof_by_shape() ? ("layernorm_f16_C" + std::to_string(C)).c_str() : "layernorm_f16", (hipStream_t)stream, 8.0 * rows * C, 4.0 * rows * C);
     hipStream_t s = (hipStream_t)stream;
     const _Float16* xh = reinterpret_cast<const _Float16*>(x); _Float16* yh = reinterpret_cast<_Float16*>(y);
     const int C8 = C / 8;

@@ -13,8 +13,8 @@
 #include <string>
 #include <vector>
 
+#include "dense_host.h"
 #include "gemm_core.h"
-#include "gemm_epilogue.h"
 
 namespace {
 
@@ -128,41 +128,27 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmParams p) {
 template <int WM, int WN, int TM, int TN>
 void launch(const GemmParams& p, hipStream_t s) {
     using T = GemmTile<WM, WN, TM, TN>;
-    static XpPerDeviceOnce attr_once;
-    if (T::kLdsBytes > 64 * 1024 && attr_once.need()) {
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<WM, WN, TM, TN, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<WM, WN, TM, TN, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-    }
-    dim3 grid(xp_cdiv(p.N, T::BN) * xp_cdiv(p.M, T::BM));
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    // one tag per kernel instantiation (tile x mode), so the HIP-event averages line up with rocprofv3's per-kernel rows
-    std::string tag = std::string(p.mode ? "conv3x3_f32_mfma_" : "gemm_f32_mfma_") + std::to_string(T::BM) + "x" + std::to_string(T::BN);
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + (p.act == 1 ? "_gelu" : "");
-    const double in_elems = p.mode == 0 ? (double)p.M * p.K : (double)p.M / (p.Ho * p.Wo) * p.Hi * p.Wi * p.Ci;
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K,
-                     4.0 * (in_elems + (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)));
+    const std::string tag = xp_dense_tag<T>(p.mode ? "conv3x3_f32_mfma_" : "gemm_f32_mfma_", "", p.M, p.N, p.K, p.act == 1);
     GemmParams q = p;
     static const bool want_stamps = getenv("XP_GEMM_STAMPS") != nullptr;
     static unsigned long long* stamp_buf = nullptr;
+    const unsigned grid = xp_cdiv(p.N, T::BN) * xp_cdiv(p.M, T::BM);
     if (want_stamps) {
         if (!stamp_buf) (void)hipMalloc(&stamp_buf, sizeof(unsigned long long) * 4 * 65536);
-        if (grid.x <= 65536) q.stamps = stamp_buf;
+        if (grid <= 65536) q.stamps = stamp_buf;
     }
-    if (p.mode == 0) hipLaunchKernelGGL((gemm_kernel<WM, WN, TM, TN, 0>), grid, dim3(T::NT), T::kLdsBytes, s, q);
-    else hipLaunchKernelGGL((gemm_kernel<WM, WN, TM, TN, 1>), grid, dim3(T::NT), T::kLdsBytes, s, q);
+    xp_dense_launch<gemm_kernel<WM, WN, TM, TN, 0>, gemm_kernel<WM, WN, TM, TN, 1>, T>(q, s, p.mode, tag, p.K, xp_dense_bytes(p, p.mode, 4.0), T::NT, 64 * 1024);
     if (q.stamps) {   // debug only: synchronises
         (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h((size_t)grid.x * 4);
+        std::vector<unsigned long long> h((size_t)grid * 4);
         (void)hipMemcpy(h.data(), stamp_buf, h.size() * 8, hipMemcpyDeviceToHost);
         double kloop = 0, epi = 0; unsigned long long tmin = ~0ull, tmax = 0;
-        for (unsigned b = 0; b < grid.x; ++b) {
+        for (unsigned b = 0; b < grid; ++b) {
             kloop += (double)(h[b * 4 + 1] - h[b * 4]); epi += (double)(h[b * 4 + 2] - h[b * 4 + 1]);
             tmin = std::min(tmin, h[b * 4]); tmax = std::max(tmax, h[b * 4 + 2]);
         }
         fprintf(stderr, "[stamps] %s grid %u: prologue+K-loop %.0f cyc, epilogue %.0f cyc per workgroup; kernel span %.0f cyc (s_memtime ticks)\n",
-                tag.c_str(), grid.x, kloop / grid.x, epi / grid.x, (double)(tmax - tmin));
+                tag.c_str(), grid, kloop / grid, epi / grid, (double)(tmax - tmin));
     }
 }
 
@@ -170,10 +156,10 @@ int dispatch(GemmParams p, hipStream_t s) {
     static const int stagger_env = getenv("XP_GEMM_STAGGER") ? atoi(getenv("XP_GEMM_STAGGER")) : -1;
     if (stagger_env >= 0) p.stagger_cycles = stagger_env;
     // tile choice by N (the encoder's N are 32..3072; M is large except at the last stage)
-    const int N = p.N;
-    if (N <= 32) launch<4, 1, 1, 1>(p, s);                                   // 128 x 32
-    else if (N <= 64) launch<4, 1, 1, 2>(p, s);                              // 128 x 64
-    else if (N <= 96 || (N % 96 == 0 && (N / 96) % 4 != 0)) launch<4, 1, 1, 3>(p, s);   // 128 x 96  (N = 65..96, 192)
+    const int N = p.N, by_n = xp_tile_by_n(N);
+    if (by_n == 0) launch<4, 1, 1, 1>(p, s);                                 // 128 x 32
+    else if (by_n == 1) launch<4, 1, 1, 2>(p, s);                            // 128 x 64
+    else if (by_n == 2) launch<4, 1, 1, 3>(p, s);                            // 128 x 96  (N = 65..96, 192)
     else if (p.M <= 8192 && N >= 512) launch<2, 2, 1, 2>(p, s);              // 64 x 128: more blocks when M is small
     else launch<2, 2, 2, 2>(p, s);                                           // 128 x 128
     XP_LAUNCH_CHECK();
@@ -185,29 +171,15 @@ int dispatch(GemmParams p, hipStream_t s) {
 extern "C" int xp_gemm_nt(const float* A, const float* Wt, float* C, const float* bias, const float* scale,
                           const float* shift, const float* res, int M, int N, int K, int lda, int ldc, int ldres,
                           int act, void* stream) {
-    XP_CHECK_ARG(A && Wt && C, "xp_gemm_nt: null pointer");
-    XP_CHECK_ARG(M > 0 && N > 0 && K > 0, "xp_gemm_nt: bad shape %d %d %d", M, N, K);
-    XP_CHECK_ARG(K % 4 == 0 && lda % 4 == 0, "xp_gemm_nt: K and lda must be multiples of 4 (got %d, %d)", K, lda);
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_gemm_nt: scale and shift go together");
-    XP_CHECK_ARG(act >= 0 && act <= 3, "xp_gemm_nt: bad act %d", act);
     GemmParams p{};
-    p.A = A; p.Wt = Wt; p.C = C; p.bias = bias; p.scale = scale; p.shift = shift; p.res = res;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.act = act; p.mode = 0;
+    XP_TRY(xp_gemm_nt_params("xp_gemm_nt", p, A, Wt, C, bias, scale, shift, res, M, N, K, lda, ldc, ldres, act));
     return dispatch(p, (hipStream_t)stream);
 }
 
 extern "C" int xp_conv3x3_nhwc(const float* x, const float* Wt, float* y, const float* bias, const float* scale,
                                const float* shift, int batch, int Hi, int Wi, int Ci, int Co, int stride,
                                int reflect_pad, int act, void* stream) {
-    XP_CHECK_ARG(x && Wt && y, "xp_conv3x3_nhwc: null pointer");
-    XP_CHECK_ARG(Ci % 4 == 0, "xp_conv3x3_nhwc: Ci must be a multiple of 4 (got %d)", Ci);
-    XP_CHECK_ARG(stride == 1 || stride == 2, "xp_conv3x3_nhwc: stride 1 or 2");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_conv3x3_nhwc: scale and shift go together");
-    XP_CHECK_ARG(!reflect_pad || (Hi >= 2 && Wi >= 2), "xp_conv3x3_nhwc: reflection pad needs H,W >= 2");
     GemmParams p{};
-    p.A = x; p.Wt = Wt; p.C = y; p.bias = bias; p.scale = scale; p.shift = shift; p.res = nullptr;
-    p.Hi = Hi; p.Wi = Wi; p.Ci = Ci; p.stride = stride; p.reflect = reflect_pad;
-    p.Ho = (Hi + 2 - 3) / stride + 1; p.Wo = (Wi + 2 - 3) / stride + 1;
-    p.M = batch * p.Ho * p.Wo; p.N = Co; p.K = 9 * Ci; p.lda = 0; p.ldc = Co; p.ldres = 0; p.act = act; p.mode = 1;
+    XP_TRY(xp_conv3x3_params("xp_conv3x3_nhwc", p, x, Wt, y, bias, scale, shift, batch, Hi, Wi, Ci, Co, stride, reflect_pad, act));
     return dispatch(p, (hipStream_t)stream);
 }

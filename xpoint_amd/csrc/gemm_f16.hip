@@ -17,7 +17,7 @@
 #include <string>
 #include <type_traits>
 
-#include "xp_common.h"
+#include "dense_host.h"
 #include "../../include/xpoint_hip.h"
 
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
@@ -267,19 +267,10 @@ __global__ __launch_bounds__(WM * WN * 64, (BK == 64 ? 2 : 4) / (WM * WN > 4 ? 2
 template <int WM, int WN, int TM, int TN, int BK>
 void f16_launch(const F16Params& p, hipStream_t s) {
     using T = F16Tile<WM, WN, TM, TN, BK>;
-    static XpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_kernel<WM, WN, TM, TN, 0, BK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_kernel<WM, WN, TM, TN, 1, BK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-    }
-    const int grid = xp_cdiv(p.M, T::BM) * xp_cdiv(p.N, T::BN);
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = std::string(p.Ci ? "conv3x3_f16_mfma_" : "gemm_f16_mfma_") + std::to_string(T::BM) + "x" + std::to_string(T::BN) + (BK == 32 ? "_k32" : "");
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K);
-    const double in_elems = p.Ci ? (double)p.M / (p.Ho * p.Wo) * p.Hi * p.Wi * p.Ci : (double)p.M * p.K;
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K, 2.0 * (in_elems + (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)) + (p.c_f32 ? 2.0 * p.M * p.N : 0.0));
-    if (p.Ci) hipLaunchKernelGGL((gemm_f16_kernel<WM, WN, TM, TN, 1, BK>), dim3(grid), dim3(T::NT), T::kLdsBytes, s, p);
-    else hipLaunchKernelGGL((gemm_f16_kernel<WM, WN, TM, TN, 0, BK>), dim3(grid), dim3(T::NT), T::kLdsBytes, s, p);
+    const bool conv = p.Ci != 0;
+    const std::string tag = xp_dense_tag<T>(conv ? "conv3x3_f16_mfma_" : "gemm_f16_mfma_", BK == 32 ? "_k32" : "", p.M, p.N, p.K, false);
+    xp_dense_launch<gemm_f16_kernel<WM, WN, TM, TN, 0, BK>, gemm_f16_kernel<WM, WN, TM, TN, 1, BK>, T>(
+        p, s, conv, tag, p.K, xp_dense_bytes(p, conv, 2.0) + (p.c_f32 ? 2.0 * p.M * p.N : 0.0), T::NT, 0);
 }
 
 int f16_dispatch(const F16Params& p, hipStream_t s) {
@@ -289,7 +280,8 @@ int f16_dispatch(const F16Params& p, hipStream_t s) {
     // Measured on the deep-stage layers (tools/gemm_bench.py, GB_F16=1, XP_F16_TILE=3/4/5): 128 x 192 wins where it covers N in fewer column tiles at short K
     // (N 192, K 768: 54.1 -> 49.8 us; N 1536, K 384 + GELU: 64.3 -> 57.4), 256 x 128 where K is long and N narrow (N 384, K 1536: 40.5 -> 35.7: the L2-read-bound
     // case of profiles/r4_03_gemm_l2_counters.txt, A re-read halves); 128 x 128 everywhere else (M 4 800 rows: larger tiles leave CUs idle).
-    int sel = N <= 32 ? 0 : N <= 64 ? 1 : (N <= 96 || (N % 96 == 0 && (N / 96) % 4 != 0)) ? 2 : 3;
+    const int by_n = xp_tile_by_n(N);
+    int sel = by_n >= 0 ? by_n : 3;
     if (!p.Ci && p.K > 192) {
         // x_proj of the deep stages (N = 4 (dt_rank + 2) = 104 / 200: one or two 128-wide column tiles over 19 200 / 4 800 rows leave most CUs idle): 128 x 32
         // tiles — 9.7 -> 8.1 us and 12.8 -> 8.4 us
@@ -347,12 +339,11 @@ extern "C" int xp_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
 
 extern "C" int xp_gemm_nt_f16(const void* A, const void* W, void* C, int c_f32, const float* bias, const float* scale, const float* shift, const void* res,
                               int M, int N, int K, int lda, int ldc, int ldres, int act, void* stream) {
-    XP_CHECK_ARG(A && W && C, "xp_gemm_nt_f16: null pointer");
-    XP_CHECK_ARG(M > 0 && N > 0 && K > 0, "xp_gemm_nt_f16: bad shape %d %d %d", M, N, K);
+    const char* who = "xp_gemm_nt_f16";
+    XP_TRY(xp_check_gemm_shape(who, A && W && C, M, N, K));
     XP_CHECK_ARG(K % 8 == 0 && lda % 8 == 0, "xp_gemm_nt_f16: K and lda must be multiples of 8 halves (got %d, %d)", K, lda);
     XP_CHECK_ARG((((uintptr_t)A | (uintptr_t)W) & 15) == 0, "xp_gemm_nt_f16: A and W must be 16-byte aligned");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_gemm_nt_f16: scale and shift go together");
-    XP_CHECK_ARG(act >= 0 && act <= 3, "xp_gemm_nt_f16: bad act %d", act);
+    XP_TRY(xp_check_epilogue(who, scale, shift, act));
     XP_CHECK_ARG(((uintptr_t)C & 15) == 0 && (!res || ((uintptr_t)res & 15) == 0), "xp_gemm_nt_f16: C and res must be 16-byte aligned");
     F16Params p{};
     p.A = (const _Float16*)A; p.W = (const _Float16*)W; p.C = C; p.bias = bias; p.scale = scale; p.shift = shift; p.res = (const _Float16*)res;
@@ -362,18 +353,11 @@ extern "C" int xp_gemm_nt_f16(const void* A, const void* W, void* C, int c_f32, 
 
 extern "C" int xp_conv3x3_nhwc_f16(const void* x, const void* W, void* y, int y_f32, const float* bias, const float* scale, const float* shift,
                                    int batch, int Hi, int Wi, int Ci, int Co, int stride, int reflect_pad, int act, void* stream) {
-    XP_CHECK_ARG(x && W && y, "xp_conv3x3_nhwc_f16: null pointer");
-    XP_CHECK_ARG(Ci % 8 == 0, "xp_conv3x3_nhwc_f16: Ci must be a multiple of 8 (got %d)", Ci);
-    XP_CHECK_ARG(stride == 1 || stride == 2, "xp_conv3x3_nhwc_f16: stride 1 or 2");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_conv3x3_nhwc_f16: scale and shift go together");
-    XP_CHECK_ARG(!reflect_pad || (Hi >= 2 && Wi >= 2), "xp_conv3x3_nhwc_f16: reflection pad needs H,W >= 2");
-    XP_CHECK_ARG((((uintptr_t)x | (uintptr_t)W | (uintptr_t)y) & 15) == 0, "xp_conv3x3_nhwc_f16: buffers must be 16-byte aligned");
     F16Params p{};
-    p.A = (const _Float16*)x; p.W = (const _Float16*)W; p.C = y; p.bias = bias; p.scale = scale; p.shift = shift; p.res = nullptr;
-    p.Hi = Hi; p.Wi = Wi; p.Ci = Ci; p.stride = stride; p.reflect = reflect_pad;
-    p.Ho = (Hi + 2 - 3) / stride + 1; p.Wo = (Wi + 2 - 3) / stride + 1;
-    p.ci_magic = (unsigned)((0x100000000ull + (unsigned)Ci - 1) / (unsigned)Ci);
+    XP_TRY(xp_conv3x3_geometry("xp_conv3x3_nhwc_f16", p, x && W && y, 8, scale, shift, batch, Hi, Wi, Ci, Co, stride, reflect_pad, act));
+    XP_CHECK_ARG((((uintptr_t)x | (uintptr_t)W | (uintptr_t)y) & 15) == 0, "xp_conv3x3_nhwc_f16: buffers must be 16-byte aligned");
     XP_CHECK_ARG(9 * Ci + 64 < 65536, "xp_conv3x3_nhwc_f16: Ci too large");
-    p.M = batch * p.Ho * p.Wo; p.N = Co; p.K = 9 * Ci; p.lda = 0; p.ldc = Co; p.ldres = 0; p.act = act; p.c_f32 = y_f32;
+    p.A = (const _Float16*)x; p.W = (const _Float16*)W; p.C = y; p.bias = bias; p.scale = scale; p.shift = shift; p.res = nullptr; p.c_f32 = y_f32;
+    p.ci_magic = (unsigned)((0x100000000ull + (unsigned)Ci - 1) / (unsigned)Ci);
     return f16_dispatch(p, (hipStream_t)stream);
 }

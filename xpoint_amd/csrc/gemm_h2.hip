@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <string>
 
+#include "dense_host.h"
 #include "gemm_h2_core.h"
 
 bool xp_gemm_h2p_applies(const GemmParams& p);      // gemm_h2p.hip: ping-pong schedule of the 128 x 128 tile
@@ -215,33 +216,16 @@ __global__ __launch_bounds__(256) void gemm_h2r_kernel(GemmParams p) {
 template <int TN>
 void launch_r(const GemmParams& p, hipStream_t s) {
     using T = GemmTileH2R<TN>;
-    dim3 grid(xp_cdiv(p.N, T::BN) * xp_cdiv(p.M, T::BM));
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = std::string(p.mode ? "conv3x3_h2r_mfma_" : "gemm_h2r_mfma_") + std::to_string(T::BM) + "x" + std::to_string(T::BN);
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + (p.act == 1 ? "_gelu" : "");
-    const double in_elems = p.mode == 0 ? (double)p.M * p.K : (double)p.M / (p.Ho * p.Wo) * p.Hi * p.Wi * p.Ci;
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K, 4.0 * (in_elems + (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)));
-    if (p.mode == 0) hipLaunchKernelGGL((gemm_h2r_kernel<TN, 0>), grid, dim3(T::NT), T::kLdsBytes, s, p);
-    else hipLaunchKernelGGL((gemm_h2r_kernel<TN, 1>), grid, dim3(T::NT), T::kLdsBytes, s, p);
+    const std::string tag = xp_dense_tag<T>(p.mode ? "conv3x3_h2r_mfma_" : "gemm_h2r_mfma_", "", p.M, p.N, p.K, p.act == 1);
+    xp_dense_launch<gemm_h2r_kernel<TN, 0>, gemm_h2r_kernel<TN, 1>, T>(p, s, p.mode, tag, p.K, xp_dense_bytes(p, p.mode, 4.0), T::NT, 48 * 1024);
 }
 
 template <int WM, int WN, int TM, int TN>
 void launch(const GemmParams& p, hipStream_t s) {
     using T = GemmTileH2<WM, WN, TM, TN>;
-    static XpPerDeviceOnce attr_once;
-    if (T::kLdsBytes > 48 * 1024 && attr_once.need()) {
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h2_kernel<WM, WN, TM, TN, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h2_kernel<WM, WN, TM, TN, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-    }
-    dim3 grid(xp_cdiv(p.N, T::BN) * xp_cdiv(p.M, T::BM));
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = std::string(p.mode ? "conv3x3_h2_mfma_" : "gemm_h2_mfma_") + std::to_string(T::BM) + "x" + std::to_string(T::BN);
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + (p.act == 1 ? "_gelu" : "");
-    const double in_elems = p.mode == 0 ? (double)p.M * p.K : (double)p.M / (p.Ho * p.Wo) * p.Hi * p.Wi * p.Ci;
+    const std::string tag = xp_dense_tag<T>(p.mode ? "conv3x3_h2_mfma_" : "gemm_h2_mfma_", "", p.M, p.N, p.K, p.act == 1);
     // flops = algorithmic 2MNK (f32-equivalent); the matrix pipe executes 3 x that in fp16
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K, 4.0 * (in_elems + (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)));
-    if (p.mode == 0) hipLaunchKernelGGL((gemm_h2_kernel<WM, WN, TM, TN, 0>), grid, dim3(T::NT), T::kLdsBytes, s, p);
-    else hipLaunchKernelGGL((gemm_h2_kernel<WM, WN, TM, TN, 1>), grid, dim3(T::NT), T::kLdsBytes, s, p);
+    xp_dense_launch<gemm_h2_kernel<WM, WN, TM, TN, 0>, gemm_h2_kernel<WM, WN, TM, TN, 1>, T>(p, s, p.mode, tag, p.K, xp_dense_bytes(p, p.mode, 4.0), T::NT, 48 * 1024);
 }
 
 int dispatch(const GemmParams& p_in, hipStream_t s) {
@@ -268,8 +252,9 @@ int dispatch(const GemmParams& p_in, hipStream_t s) {
     static const int no64 = getenv("XP_H2_NO64") ? atoi(getenv("XP_H2_NO64")) : 2;
     const int64_t t128 = (int64_t)xp_cdiv(p.M, 128) * xp_cdiv(N, 128);
     const bool want64 = no64 == 1 ? false : no64 == 2 ? t128 < 128 : ((p.M <= 8192 && N >= 512 && t128 < 512) || t128 < 256);
+    const int by_n = xp_tile_by_n(N);
     const int sel = force >= 0 ? force
-                  : N <= 32 ? 0 : N <= 64 ? 1 : (N <= 96 || (N % 96 == 0 && (N / 96) % 4 != 0)) ? 2
+                  : by_n >= 0 ? by_n
                   : want64 ? 3 : 4;       // fewer 128 x 128 tiles than CUs (x_proj of the deep stages: N = 104 / 200): 64 x 128
     // Row-stationary engine for the implicit-GEMM convolutions (measured: 0.55 vs 0.71 ms for the four big convs of a step; the gathered
     // A rows cost the tile engine an LDS round trip they do not need), the tile engine for plain GEMMs (equal at K >= 384, 15 % faster at
@@ -306,11 +291,6 @@ extern "C" size_t xp_split_weights_h2_bytes(int N, int K) {
     return (size_t)N * ((K + H2_BK - 1) / H2_BK) * H2_SLAB_UNITS * 16 + (((size_t)N * 4 + 15) & ~(size_t)15);
 }
 
-// planes first, the N inverse row scales (f32) right behind them
-static const float* h2_scales(const void* Wh2, int N, int K) {
-    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(Wh2) + (size_t)N * ((K + H2_BK - 1) / H2_BK) * H2_SLAB_UNITS * 16);
-}
-
 extern "C" int xp_split_weights_h2(const float* W, void* out, int N, int K, void* stream) {
     XP_CHECK_ARG(W && out, "xp_split_weights_h2: null pointer");
     XP_CHECK_ARG(N > 0 && K > 0, "xp_split_weights_h2: bad shape %d %d", N, K);
@@ -326,30 +306,16 @@ extern "C" int xp_split_weights_h2(const float* W, void* out, int N, int K, void
 
 extern "C" int xp_gemm_nt_h2(const float* A, const void* Wh2, float* C, const float* bias, const float* scale, const float* shift,
                              const float* res, int M, int N, int K, int lda, int ldc, int ldres, int act, void* stream) {
-    XP_CHECK_ARG(A && Wh2 && C, "xp_gemm_nt_h2: null pointer");
-    XP_CHECK_ARG(M > 0 && N > 0 && K > 0, "xp_gemm_nt_h2: bad shape %d %d %d", M, N, K);
-    XP_CHECK_ARG(K % 4 == 0 && lda % 4 == 0, "xp_gemm_nt_h2: K and lda must be multiples of 4 (got %d, %d)", K, lda);
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_gemm_nt_h2: scale and shift go together");
-    XP_CHECK_ARG(act >= 0 && act <= 3, "xp_gemm_nt_h2: bad act %d", act);
     GemmParams p{};
-    p.A = A; p.Wt = (const float*)Wh2; p.C = C; p.bias = bias; p.scale = scale; p.shift = shift; p.res = res; p.wscale = h2_scales(Wh2, N, K);
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.act = act; p.mode = 0;
-    p.r16 = xp_amp_value();
+    XP_TRY(xp_gemm_nt_params("xp_gemm_nt_h2", p, A, Wh2, C, bias, scale, shift, res, M, N, K, lda, ldc, ldres, act));
+    p.wscale = h2_scales(Wh2, N, K); p.r16 = xp_amp_value();
     return dispatch(p, (hipStream_t)stream);
 }
 
 extern "C" int xp_conv3x3_nhwc_h2(const float* x, const void* Wh2, float* y, const float* bias, const float* scale, const float* shift,
                                   int batch, int Hi, int Wi, int Ci, int Co, int stride, int reflect_pad, int act, void* stream) {
-    XP_CHECK_ARG(x && Wh2 && y, "xp_conv3x3_nhwc_h2: null pointer");
-    XP_CHECK_ARG(Ci % 4 == 0, "xp_conv3x3_nhwc_h2: Ci must be a multiple of 4 (got %d)", Ci);
-    XP_CHECK_ARG(stride == 1 || stride == 2, "xp_conv3x3_nhwc_h2: stride 1 or 2");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_conv3x3_nhwc_h2: scale and shift go together");
-    XP_CHECK_ARG(!reflect_pad || (Hi >= 2 && Wi >= 2), "xp_conv3x3_nhwc_h2: reflection pad needs H,W >= 2");
     GemmParams p{};
-    p.A = x; p.Wt = (const float*)Wh2; p.C = y; p.bias = bias; p.scale = scale; p.shift = shift; p.res = nullptr; p.wscale = h2_scales(Wh2, Co, 9 * Ci);
-    p.Hi = Hi; p.Wi = Wi; p.Ci = Ci; p.stride = stride; p.reflect = reflect_pad;
-    p.Ho = (Hi + 2 - 3) / stride + 1; p.Wo = (Wi + 2 - 3) / stride + 1;
-    p.M = batch * p.Ho * p.Wo; p.N = Co; p.K = 9 * Ci; p.lda = 0; p.ldc = Co; p.ldres = 0; p.act = act; p.mode = 1;
-    p.r16 = xp_amp_value();
+    XP_TRY(xp_conv3x3_params("xp_conv3x3_nhwc_h2", p, x, Wh2, y, bias, scale, shift, batch, Hi, Wi, Ci, Co, stride, reflect_pad, act));
+    p.wscale = h2_scales(Wh2, p.N, p.K); p.r16 = xp_amp_value();
     return dispatch(p, (hipStream_t)stream);
 }

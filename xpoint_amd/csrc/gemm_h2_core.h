@@ -40,6 +40,11 @@ typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 constexpr int H2_BK = 32;           // k per slab
 constexpr int H2_ROWB = 144;        // LDS bytes per tile row
 constexpr int H2_SLAB_UNITS = 8;    // 16-byte units per (weight row, slab) in the offline layout: 2 planes x 4 octets
+// The offline weight buffer (xp_split_weights_h2): the planes first, the N inverse row scales (f32) right behind them.  With whole slabs (K % 32 == 0: the ring
+// engine's K = 32 T) the offset is N * T * H2_SLAB_UNITS * 16 = N * T * 128 bytes.
+static inline const float* h2_scales(const void* Wh2, int N, int K) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(Wh2) + (size_t)N * ((K + H2_BK - 1) / H2_BK) * H2_SLAB_UNITS * 16);
+}
 
 __device__ __forceinline__ void h2_lds_barrier() {
     if (XP_H2_DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -14,6 +14,7 @@
 // workgroup, 2 x 36 KB of LDS, one workgroup (8 waves) per CU.  Summation order differs from the tile kernel (even slabs + odd slabs); same class.
 #include <stdlib.h>
 
+#include "dense_host.h"
 #include "gemm_h2_core.h"
 
 namespace {
@@ -21,6 +22,7 @@ namespace {
 constexpr int P_BM = 128, P_BN = 128;
 constexpr int P_BUF = (P_BM + P_BN) * H2_ROWB;           // [A rows: 2 planes][B rows: 2 planes], 144-byte rows
 constexpr size_t P_LDS = 2 * (size_t)P_BUF;              // 73 728 B
+struct PHostTile { static constexpr int BM = P_BM, BN = P_BN; static constexpr size_t kLdsBytes = P_LDS; };      // what xp_dense_launch asks of a tile
 constexpr int P_ALD = 4, P_BLD = 4;                      // staging slots per thread of the staging group and slab (256 threads: 1024 A quads, 1024 B units)
 
 #ifndef XP_H2P_DBG
@@ -248,16 +250,9 @@ bool xp_gemm_h2p_applies(const GemmParams& p) {
 }
 
 int xp_gemm_h2p_launch(const GemmParams& p, hipStream_t s) {
-    static XpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        XP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P_LDS));
-    }
-    const int grid = xp_cdiv(p.M, P_BM) * xp_cdiv(p.N, P_BN);
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = "gemm_h2p_mfma_128x128";
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + (p.act == 1 ? "_gelu" : "");
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)));
-    hipLaunchKernelGGL(gemm_h2p_kernel, dim3(grid), dim3(512), P_LDS, s, p);
+    const std::string tag = xp_dense_tag<PHostTile>("gemm_h2p_mfma_", "", p.M, p.N, p.K, p.act == 1);
+    // always opts in (72 KB), and a failed opt-in returns here instead of going on to a launch that cannot succeed
+    XP_TRY((xp_dense_launch<gemm_h2p_kernel, gemm_h2p_kernel, PHostTile>(p, s, false, tag, p.K, xp_dense_bytes(p, false, 4.0), 512, 0, true)));
     XP_LAUNCH_CHECK();
     if (XP_H2P_DBG & 64) {      // debug builds only: synchronises
         static int printed = 0;

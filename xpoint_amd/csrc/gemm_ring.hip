@@ -13,26 +13,23 @@
 
 #include <string>
 
+#include "dense_host.h"
+#include "gemm_h2_core.h"
 #include "ring_core.h"
 #include "../../include/xpoint_hip.h"
 
 namespace {
 
 template <int GM, int GN, int TM, int TN, int PL, int S>
-void ring_launch(const RingParams& p, hipStream_t s, const char* name, double flops, double bytes) {
+void ring_launch(const RingParams& p, hipStream_t s, const char* name, double bytes) {
     using T = RingTile<GM, GN, TM, TN, PL, S>;
-    static XpPerDeviceOnce attr_once;
-    if (attr_once.need()) XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&ring_gemm_kernel<GM, GN, TM, TN, PL, S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-    const int grid = xp_cdiv(p.M, T::BM) * xp_cdiv(p.N, T::BN);
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = std::string(name) + "_" + std::to_string(T::BM) + "x" + std::to_string(T::BN);
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.T * (PL == 1 ? 64 : 32)) + (p.act == 1 ? "_gelu" : "");
-    XpProfScope prof(tag.c_str(), s, flops, bytes);
-    hipLaunchKernelGGL((ring_gemm_kernel<GM, GN, TM, TN, PL, S>), dim3(grid), dim3(512), T::kLdsBytes, s, p);
+    const int K = p.T * (PL == 1 ? 64 : 32);
+    const std::string tag = xp_dense_tag<T>(std::string(name) + "_", "", p.M, p.N, K, p.act == 1);
+    xp_dense_launch<ring_gemm_kernel<GM, GN, TM, TN, PL, S>, ring_gemm_kernel<GM, GN, TM, TN, PL, S>, T>(p, s, false, tag, K, bytes, 512, 0);
 }
 
 template <int PL>
-void ring_dispatch(RingParams& p, hipStream_t s, const char* name, double flops, double bytes) {
+void ring_dispatch(RingParams& p, hipStream_t s, const char* name, double bytes) {
     static const int force = getenv("XP_RING_TILE") ? atoi(getenv("XP_RING_TILE")) : -1;      // tuning experiments only: 0 = 256 x 256, 1 = 256 x 128, 2 = 128 x 128
     auto tiles = [&](int bm, int bn) { return (int64_t)xp_cdiv(p.M, bm) * xp_cdiv(p.N, bn); };
     int sel = tiles(256, 256) >= 192 && p.N > 128 ? 0 : tiles(256, 128) >= 192 ? 1 : 2;
@@ -49,9 +46,9 @@ void ring_dispatch(RingParams& p, hipStream_t s, const char* name, double flops,
         }
     }
     switch (sel) {
-        case 0: ring_launch<2, 2, 2, 4, PL, 2>(p, s, name, flops, bytes); break;
-        case 1: ring_launch<2, 2, 2, 2, PL, 3>(p, s, name, flops, bytes); break;
-        default: ring_launch<1, 4, 2, 1, PL, 4>(p, s, name, flops, bytes); break;
+        case 0: ring_launch<2, 2, 2, 4, PL, 2>(p, s, name, bytes); break;
+        case 1: ring_launch<2, 2, 2, 2, PL, 3>(p, s, name, bytes); break;
+        default: ring_launch<1, 4, 2, 1, PL, 4>(p, s, name, bytes); break;
     }
 }
 
@@ -100,16 +97,15 @@ extern "C" int xp_gemm_nt_h2s_applies(int N, int K) {
 
 extern "C" int xp_gemm_nt_h2s(const void* A_p32, const void* Wh2, void* C, int out_fmt, const float* bias, const float* scale, const float* shift,
                               const float* res, int M, int N, int K, int ldc, int ldres, int act, void* stream) {
-    XP_CHECK_ARG(A_p32 && Wh2 && C, "xp_gemm_nt_h2s: null pointer");
-    XP_CHECK_ARG(M > 0 && N > 0 && K > 0, "xp_gemm_nt_h2s: bad shape %d %d %d", M, N, K);
+    const char* who = "xp_gemm_nt_h2s";
+    XP_TRY(xp_check_gemm_shape(who, A_p32 && Wh2 && C, M, N, K));
     XP_CHECK_ARG(K % 32 == 0, "xp_gemm_nt_h2s: K must be a multiple of 32 (whole P32 slabs; got %d)", K);
     XP_CHECK_ARG(N % 8 == 0, "xp_gemm_nt_h2s: N must be a multiple of 8 (got %d)", N);
     XP_CHECK_ARG(out_fmt == RG_F32 || out_fmt == RG_P32, "xp_gemm_nt_h2s: out_fmt must be 0 (f32 rows) or 2 (P32 image)");
     XP_CHECK_ARG(out_fmt != RG_P32 || (N % 32 == 0 && ldc == N), "xp_gemm_nt_h2s: a P32 output needs N %% 32 == 0 and ldc == N (got %d, %d)", N, ldc);
     XP_CHECK_ARG(ldc % 4 == 0 && (!res || ldres % 4 == 0), "xp_gemm_nt_h2s: ldc / ldres must be multiples of 4");
     XP_CHECK_ARG((((uintptr_t)A_p32 | (uintptr_t)Wh2 | (uintptr_t)C | (uintptr_t)res) & 15) == 0, "xp_gemm_nt_h2s: buffers must be 16-byte aligned");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_gemm_nt_h2s: scale and shift go together");
-    XP_CHECK_ARG(act >= 0 && act <= 3, "xp_gemm_nt_h2s: bad act %d", act);
+    XP_TRY(xp_check_epilogue(who, scale, shift, act));
     XP_CHECK_ARG(!xp_amp_value(), "xp_gemm_nt_h2s: the f32-container mixed-precision class (xp_set_amp_mode) runs on xp_gemm_nt_h2");
     const int T = K / 32;
     XP_CHECK_ARG((int64_t)M * T * 128 < (1ll << 32) && (int64_t)N * T * 128 < (1ll << 32), "xp_gemm_nt_h2s: operand images must stay below 4 GB");
@@ -118,9 +114,9 @@ extern "C" int xp_gemm_nt_h2s(const void* A_p32, const void* Wh2, void* C, int o
     p.a_row = (int64_t)T * 128; p.a_slab = 128; p.w_row = 128; p.w_slab = (int64_t)N * 128;
     p.M = M; p.N = N; p.T = T;
     p.C = C; p.ldc = ldc; p.out_fmt = out_fmt;
-    p.wscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(Wh2) + (size_t)N * T * 128);      // the inverse row scales sit right behind the planes
+    p.wscale = h2_scales(Wh2, N, K);
     p.bias = bias; p.scale = scale; p.shift = shift; p.res = res; p.ldres = ldres; p.res_fmt = RG_F32; p.act = act; p.r16 = 0;
-    ring_dispatch<2>(p, (hipStream_t)stream, "gemm_ring_h2s", 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (res ? 2 : 1)));
+    ring_dispatch<2>(p, (hipStream_t)stream, "gemm_ring_h2s", 4.0 * ((double)M * K + (double)N * K + (double)M * N * (res ? 2 : 1)));
     XP_LAUNCH_CHECK();
     return XP_OK;
 }

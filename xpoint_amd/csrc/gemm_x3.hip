@@ -10,6 +10,7 @@
 
 #include <string>
 
+#include "dense_host.h"
 #include "gemm_x3_core.h"
 
 namespace {
@@ -105,24 +106,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_x3_kernel(GemmParams p) {
 template <int WM, int WN, int TM, int TN, int NP>
 void launch_np(const GemmParams& p, hipStream_t s) {
     using T = GemmTileX3<WM, WN, TM, TN, NP>;
-    static XpPerDeviceOnce attr_once;
-    if (T::kLdsBytes > 48 * 1024 && attr_once.need()) {
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<WM, WN, TM, TN, 0, NP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-        XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<WM, WN, TM, TN, 1, NP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::kLdsBytes));
-    }
-    dim3 grid(xp_cdiv(p.N, T::BN) * xp_cdiv(p.M, T::BM));
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    std::string tag = std::string(p.mode ? "conv3x3_x3_mfma_" : "gemm_x3_mfma_") + std::to_string(T::BM) + "x" + std::to_string(T::BN);
-    if (NP != 6) tag += "_np" + std::to_string(NP);
-    if (by_shape) tag += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + (p.act == 1 ? "_gelu" : "");
-    const double in_elems = p.mode == 0 ? (double)p.M * p.K : (double)p.M / (p.Ho * p.Wo) * p.Hi * p.Wi * p.Ci;
-    // flops = algorithmic 2MNK (f32-equivalent); the matrix pipe executes NP x that in bf16
-    XpProfScope prof(tag.c_str(), s, 2.0 * p.M * p.N * p.K,
-                     4.0 * (in_elems + 1.5 * (double)p.N * p.K + (double)p.M * p.N * (p.res ? 2 : 1)));
-    if (p.mode == 0) hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, TM, TN, 0, NP>), grid, dim3(T::NT), T::kLdsBytes, s, p);
-    else hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, TM, TN, 1, NP>), grid, dim3(T::NT), T::kLdsBytes, s, p);
+    const std::string tag = xp_dense_tag<T>(p.mode ? "conv3x3_x3_mfma_" : "gemm_x3_mfma_", NP != 6 ? "_np" + std::to_string(NP) : "", p.M, p.N, p.K, p.act == 1);
+    // flops = algorithmic 2MNK (f32-equivalent); the matrix pipe executes NP x that in bf16.  Weights: three bf16 planes = 1.5 f32 containers per element
+    xp_dense_launch<gemm_x3_kernel<WM, WN, TM, TN, 0, NP>, gemm_x3_kernel<WM, WN, TM, TN, 1, NP>, T>(p, s, p.mode, tag, p.K, xp_dense_bytes(p, p.mode, 4.0, 1.5),
+                                                                                                      T::NT, 48 * 1024);
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -135,7 +122,6 @@ void launch(const GemmParams& p, hipStream_t s) {
 }
 
 int dispatch(const GemmParams& p, hipStream_t s) {
-    const int N = p.N;
     static const int force = getenv("XP_X3_TILE") ? atoi(getenv("XP_X3_TILE")) : -1;   // tuning experiments only
     if (force >= 0) {
         switch (force) {
@@ -148,9 +134,10 @@ int dispatch(const GemmParams& p, hipStream_t s) {
         XP_LAUNCH_CHECK();
         return XP_OK;
     }
-    if (N <= 32) launch<4, 1, 1, 1>(p, s);                                   // 128 x 32
-    else if (N <= 64) launch<4, 1, 1, 2>(p, s);                              // 128 x 64
-    else if (N <= 96 || (N % 96 == 0 && (N / 96) % 4 != 0)) launch<4, 1, 1, 3>(p, s);   // 128 x 96  (N = 65..96, 192)
+    const int N = p.N, by_n = xp_tile_by_n(N);
+    if (by_n == 0) launch<4, 1, 1, 1>(p, s);                                 // 128 x 32
+    else if (by_n == 1) launch<4, 1, 1, 2>(p, s);                            // 128 x 64
+    else if (by_n == 2) launch<4, 1, 1, 3>(p, s);                            // 128 x 96  (N = 65..96, 192)
     else if (p.M <= 8192 && N >= 512 && (int64_t)xp_cdiv(p.M, 128) * xp_cdiv(N, 128) < 512)
         launch<2, 2, 1, 2>(p, s);                                            // 64 x 128: more blocks when 128 x 128 tiles would not fill the 2 x 256 slots once
     else launch<2, 2, 2, 2>(p, s);                                           // 128 x 128
@@ -180,29 +167,15 @@ extern "C" int xp_split_weights_x3(const float* W, void* out, int N, int K, void
 extern "C" int xp_gemm_nt_x3(const float* A, const void* Wx3, float* C, const float* bias, const float* scale,
                              const float* shift, const float* res, int M, int N, int K, int lda, int ldc, int ldres,
                              int act, void* stream) {
-    XP_CHECK_ARG(A && Wx3 && C, "xp_gemm_nt_x3: null pointer");
-    XP_CHECK_ARG(M > 0 && N > 0 && K > 0, "xp_gemm_nt_x3: bad shape %d %d %d", M, N, K);
-    XP_CHECK_ARG(K % 4 == 0 && lda % 4 == 0, "xp_gemm_nt_x3: K and lda must be multiples of 4 (got %d, %d)", K, lda);
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_gemm_nt_x3: scale and shift go together");
-    XP_CHECK_ARG(act >= 0 && act <= 3, "xp_gemm_nt_x3: bad act %d", act);
     GemmParams p{};
-    p.A = A; p.Wt = (const float*)Wx3; p.C = C; p.bias = bias; p.scale = scale; p.shift = shift; p.res = res;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.act = act; p.mode = 0;
+    XP_TRY(xp_gemm_nt_params("xp_gemm_nt_x3", p, A, Wx3, C, bias, scale, shift, res, M, N, K, lda, ldc, ldres, act));
     return dispatch(p, (hipStream_t)stream);
 }
 
 extern "C" int xp_conv3x3_nhwc_x3(const float* x, const void* Wx3, float* y, const float* bias, const float* scale,
                                   const float* shift, int batch, int Hi, int Wi, int Ci, int Co, int stride,
                                   int reflect_pad, int act, void* stream) {
-    XP_CHECK_ARG(x && Wx3 && y, "xp_conv3x3_nhwc_x3: null pointer");
-    XP_CHECK_ARG(Ci % 4 == 0, "xp_conv3x3_nhwc_x3: Ci must be a multiple of 4 (got %d)", Ci);
-    XP_CHECK_ARG(stride == 1 || stride == 2, "xp_conv3x3_nhwc_x3: stride 1 or 2");
-    XP_CHECK_ARG((scale == nullptr) == (shift == nullptr), "xp_conv3x3_nhwc_x3: scale and shift go together");
-    XP_CHECK_ARG(!reflect_pad || (Hi >= 2 && Wi >= 2), "xp_conv3x3_nhwc_x3: reflection pad needs H,W >= 2");
     GemmParams p{};
-    p.A = x; p.Wt = (const float*)Wx3; p.C = y; p.bias = bias; p.scale = scale; p.shift = shift; p.res = nullptr;
-    p.Hi = Hi; p.Wi = Wi; p.Ci = Ci; p.stride = stride; p.reflect = reflect_pad;
-    p.Ho = (Hi + 2 - 3) / stride + 1; p.Wo = (Wi + 2 - 3) / stride + 1;
-    p.M = batch * p.Ho * p.Wo; p.N = Co; p.K = 9 * Ci; p.lda = 0; p.ldc = Co; p.ldres = 0; p.act = act; p.mode = 1;
+    XP_TRY(xp_conv3x3_params("xp_conv3x3_nhwc_x3", p, x, Wx3, y, bias, scale, shift, batch, Hi, Wi, Ci, Co, stride, reflect_pad, act));
     return dispatch(p, (hipStream_t)stream);
 }

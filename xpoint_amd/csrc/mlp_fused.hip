@@ -593,12 +593,11 @@ int launch_mlp_np(const MlpParams& p, hipStream_t s) {
         XP_HIP_WARN(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<C, NW, MODE, NP, H2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   3 * T::IMGP + 4096 * 4 * (H2 ? 2 : 1)));
     }
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
     const char* eng = H2 ? "_h2_c" : "_x3_c";
     std::string tag = std::string(MODE == 2 ? "ln_proj" : PRE ? "proj_mlp_fused" : "mlp_fused") + eng + std::to_string(C);      // one tag per kernel instance
     if (NP != 6 && !H2) tag += "_np" + std::to_string(NP);
     if (NW == 8 && !H2) tag += "_nw8";                                                                    // XP_MLP_NW8 only
-    if (by_shape) tag += "_M" + std::to_string(p.M);
+    if (xp_prof_by_shape()) tag += "_M" + std::to_string(p.M);
     // flops = algorithmic 2*M*C*H4 per GEMM (f32-equivalent); bytes: x read twice (LN input, residual) and written once
     XpProfScope prof(tag.c_str(), s, MODE == 2 ? 2.0 * p.M * C * (double)p.Nout : 4.0 * p.M * C * (double)p.H4 + (PRE ? 2.0 * p.M * C * (double)C : 0.0),
                      MODE == 2 ? 4.0 * p.M * (C + (double)p.Nout) + 6.0 * C * (double)p.Nout : (PRE ? 20.0 : 12.0) * p.M * C + 12.0 * C * (double)p.H4);

@@ -940,8 +940,7 @@ bool seq_scan2_applies(int R, int H, int W, int C) {
 template <int R>
 int launch_ss2d_seq(const SS2DParams& p, float* ys, hipStream_t s, bool half_out = false) {
     const double MC = (double)p.Bn * p.H * p.W * p.C, MX = (double)p.Bn * p.H * p.W * 4 * (R + 2);
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    const std::string sfx = by_shape ? "_C" + std::to_string(p.C) : std::string();
+    const std::string sfx = xp_prof_by_shape() ? "_C" + std::to_string(p.C) : std::string();
     {   // every route reads u and its quarter of xdbl, writes its y
         XpProfScope prof(("ss2d_seq_scan" + sfx).c_str(), s, 4.0 * MC * (2.0 * R + 14.0), 4.0 * (8.0 * MC + MX));
         const bool v2 = seq_scan2_applies(R, p.H, p.W, p.C);
@@ -1004,8 +1003,7 @@ int launch_ss2d(const SS2DParams& p, hipStream_t s, bool half_io = false) {
     const size_t sm3 = sm1 + sizeof(float) * (size_t)npx * (p.C + 8);
     dim3 grid1(xp_cdiv(p.nc, p.cpb), p.Bn, 2), grid3(xp_cdiv(p.nc, p.cpb), p.Bn, 1);
     const double MC = (double)p.Bn * p.H * p.W * p.C, MX = (double)p.Bn * p.H * p.W * XW;
-    static const bool by_shape = getenv("XP_PROF_SHAPES") != nullptr;
-    const std::string sfx = by_shape ? "_C" + std::to_string(p.C) : std::string();
+    const std::string sfx = xp_prof_by_shape() ? "_C" + std::to_string(p.C) : std::string();
     const double el = 4.0 * MC;   // (pixel, channel, direction) scan elements of the whole core
     {   // reads u + its half of xdbl for each of the two route pairs
         XpProfScope prof(("ss2d_pass1" + sfx).c_str(), s, el * (2.0 * R + 12.0) / 2.0, 4.0 * 2.0 * (MC + MX));

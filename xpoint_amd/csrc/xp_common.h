@@ -56,6 +56,8 @@ private:
     hipStream_t stream_;
     size_t index_ = 0;
 };
+// Whether the tags carry the launch's shape (XP_PROF_SHAPES; api.cpp).
+bool xp_prof_by_shape();
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: one "done" flag per device ordinal (a process that drives several GPUs
 // would otherwise launch with > 64 KB of dynamic LDS on the second device without the opt-in).  `static XpPerDeviceOnce once; if (once.need()) XP_HIP(...)`.

@@ -47,7 +47,7 @@ static const XpKnob kXpKnobs[] = {
     {"XP_NMS_SWEEP", "postproc.hip", "NMS sweep count"},
     {"XP_NMS_WIDE_ROUNDS", "postproc.hip", "wide suppression rounds ahead of the NMS finisher"},
     // ---- profiling
-    {"XP_PROF_SHAPES", "*.hip", "1: per-shape tags in the HIP-event breakdown (xp_prof_*)"},
+    {"XP_PROF_SHAPES", "api.cpp", "1: per-shape tags in the HIP-event breakdown (xp_prof_*)"},
     // ---- host side (Python)
     {"XP_GEMM_MODE", "models.py / bench.py", "default gemm_mode of models.XPoint: h2 | x3 | f32 | x2 | bf16 | amp16 | amp16f"},
     {"XP_HONOR_MIXED_PRECISION", "models.py", "1: take the precision class from the config's mixed_precision flag"},
