@@ -209,7 +209,47 @@ __global__ __launch_bounds__(256) void gemm_h2r_kernel(GemmParams p) {
     auto ldB = [&](int s, int t) -> uint4 { return w_unit[s][(t < nslab ? t : nslab - 1) * w_slab]; };
 
     f32x16 acc[1][TN];
-    T::run(lds_h2, p.K, ldA8, ldB, acc);
+    // Convolution with Ci % 16 == 0 over an image batch below 2 GB (every convolution of the models; wave-uniform): a 16-wide k-step lies inside ONE tap, the
+    // same for both halves of the wave, so (tap, ci) advance as scalars and the lane's pixel geometry — division, reflection or padding test, address — is
+    // worked out once per tap (nine times per launch, behind a wave-uniform branch) as a 32-bit byte offset from the tensor base, not twice per slab.  The
+    // loads go through a buffer resource over the whole input: a padded tap, and a k-step past K, carry an offset beyond its end and the hardware returns
+    // zeros, so the split masks nothing (T::run<false>).  Same values in the same order as the general form below: the same bits.
+    // The test is made here, not on the host: M = batch * Ho * Wo exactly (xp_conv3x3_geometry), so the division gives the batch.  The limit is 2 GB, not the
+    // 4 GB a 32-bit offset could reach, because kPastEnd must lie beyond every input.  Every <TN, 1> instance holds both forms; the general form is what
+    // Ci = 8, 24, 40 run (tests), its use for an input of 2 GB or more is compiled but not exercised by any test.
+    const int64_t in_bytes = MODE == 1 ? (int64_t)(p.M / (p.Ho * p.Wo)) * p.Hi * p.Wi * p.Ci * 4 : 0;
+    if (MODE == 1 && p.Ci % 16 == 0 && in_bytes < (1ll << 31)) {
+        constexpr unsigned kPastEnd = 0x80000000u;             // >= in_bytes, and no 32-bit wrap when the channel offset is added
+        const unsigned lane_base = (unsigned)(a_ptr - p.A) * 4u + (unsigned)fh * 32u;       // the lane's image and its half of the k-step
+        auto tap_offset = [&](int tap) -> unsigned {
+            if (tap >= 9) return kPastEnd;
+            int ih = a_oh + tap / 3, iw = a_ow + tap % 3;
+            bool real = true;
+            if (p.reflect) {
+                ih = ih < 0 ? -ih : (ih >= p.Hi ? 2 * p.Hi - 2 - ih : ih);
+                iw = iw < 0 ? -iw : (iw >= p.Wi ? 2 * p.Wi - 2 - iw : iw);
+            } else {
+                real = ih >= 0 && ih < p.Hi && iw >= 0 && iw < p.Wi;
+            }
+            return real ? lane_base + (unsigned)((ih * p.Wi + iw) * p.Ci) * 4u : kPastEnd;
+        };
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)in_bytes, 0x00020000);
+        int tap = 0, ci4 = 0;                                   // of the next k-step: wave-uniform (ci4 = byte offset of its first channel)
+        unsigned cur = tap_offset(0);
+        typedef unsigned raw4 __attribute__((ext_vector_type(4)));
+        auto ldA8c = [&](int, float4& lo, float4& hi) -> bool {
+            const raw4 a = __builtin_bit_cast(raw4, __builtin_amdgcn_raw_buffer_load_b128(rs, cur, ci4, 0));
+            const raw4 b = __builtin_bit_cast(raw4, __builtin_amdgcn_raw_buffer_load_b128(rs, cur + 16, ci4, 0));
+            lo = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
+            hi = make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
+            ci4 += 64;
+            if (ci4 == p.Ci * 4) { ci4 = 0; ++tap; cur = tap_offset(tap); }
+            return true;
+        };
+        T::template run<false>(lds_h2, p.K, ldA8c, ldB, acc);
+    } else {
+        T::run(lds_h2, p.K, ldA8, ldB, acc);
+    }
     gemm_epilogue<T, 1, TN, true>(p, m0, n0, acc);
 }
 

@@ -248,8 +248,10 @@ struct GemmTileH2R {
 
     // ldA8(k, lo, hi) -> ok: the 8 consecutive f32 of THIS LANE's row starting at absolute k (a multiple of 8), loaded unconditionally
     //                        from a valid address; ok = real (else they count as zeros).  Called twice per slab, in k order.
+    //                        MASK = false: the loader itself delivers zeros for what is not real (a bounded buffer load), `ok` is not looked at and
+    //                        the split does not mask its input.
     // ldB(slot, slab)      : as in GemmTileH2.
-    template <class LA, class LB>
+    template <bool MASK = true, class LA, class LB>
     __device__ static __forceinline__ void run(unsigned char* lds, int K, LA ldA8, LB ldB, f32x16 (&acc)[1][TN]) {
         const int lane = threadIdx.x & 63;
         const int fr = lane & 31, fh = lane >> 5;
@@ -264,8 +266,10 @@ struct GemmTileH2R {
         auto split = [&](const RawA& r, PlanesA& o) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const unsigned m = r.ok[s] ? 0xffffffffu : 0u;
-                auto mk = [&](float v) { return __uint_as_float(__float_as_uint(v) & m); };
+                auto mk = [&](float v) {
+                    if constexpr (MASK) return __uint_as_float(__float_as_uint(v) & (r.ok[s] ? 0xffffffffu : 0u));
+                    else return v;
+                };
                 uint2 a0, a1, b0, b1;
                 h2_split4(make_float4(mk(r.lo[s].x), mk(r.lo[s].y), mk(r.lo[s].z), mk(r.lo[s].w)), a0, a1);
                 h2_split4(make_float4(mk(r.hi[s].x), mk(r.hi[s].y), mk(r.hi[s].z), mk(r.hi[s].w)), b0, b1);
