@@ -1,6 +1,6 @@
 """The fp16-storage mixed-precision class ("amp16f") kernel by kernel against the float64 restatement of its recipe (tests/amp_recipe64.py):
 the fused SS2D core in both of its forms and in every NW regime of the sequential one, the same recipe in f32 containers ("amp16": xp_set_amp_mode(1) +
-xp_ss2d_core_fwd), the glue kernels of csrc/elementwise_f16.hip and the two conversions that are the recipe's rounding points.  The class's GEMM-type
+xp_ss2d_core_fwd), the glue kernels of csrc/elementwise_f16.hip (stem, dwconv and depth-to-space: the shared bodies of csrc/glue_core.h) and the two conversions that are the recipe's rounding points.  The class's GEMM-type
 kernels are pinned in test_gpu_h2.py.
 
 Every output sits in a canary allocation (test_gpu_batch_invariance.Canary) whose padding must survive the call, and the profiling tags prove which form

@@ -7,7 +7,7 @@
 
 #include <algorithm>
 
-#include "xp_common.h"
+#include "glue_core.h"
 
 namespace {
 
@@ -109,13 +109,12 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
                 o.z = (v[r][i].z - mean) * rstd * wv.z + bv.z; o.w = (v[r][i].w - mean) * rstd * wv.w + bv.w;
                 if (gelu) { o.x = xp_gelu(o.x); o.y = xp_gelu(o.y); o.z = xp_gelu(o.z); o.w = xp_gelu(o.w); }
                 if (P32) {
-                    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                    const h4 hi = {(_Float16)o.x, (_Float16)o.y, (_Float16)o.z, (_Float16)o.w};
-                    const h4 lo = {(_Float16)(o.x - (float)hi[0]), (_Float16)(o.y - (float)hi[1]), (_Float16)(o.z - (float)hi[2]), (_Float16)(o.w - (float)hi[3])};
+                    const xp_h4 hi = {(_Float16)o.x, (_Float16)o.y, (_Float16)o.z, (_Float16)o.w};
+                    const xp_h4 lo = {(_Float16)(o.x - (float)hi[0]), (_Float16)(o.y - (float)hi[1]), (_Float16)(o.z - (float)hi[2]), (_Float16)(o.w - (float)hi[3])};
                     const int c = c4 * 4;
                     unsigned char* op = reinterpret_cast<unsigned char*>(y) + ((row0 + r * RPW) * (C >> 5) + (c >> 5)) * 128 + (c & 31) * 2;
-                    *reinterpret_cast<h4*>(op) = hi;
-                    *reinterpret_cast<h4*>(op + 64) = lo;
+                    *reinterpret_cast<xp_h4*>(op) = hi;
+                    *reinterpret_cast<xp_h4*>(op + 64) = lo;
                 } else
                 yr[c4] = o;
             }
@@ -124,13 +123,9 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Depthwise 3x3 (zero pad 1, no bias) + SiLU, NHWC.  Reference VMamba.py:655-658.
-// weight layout [9][C] (tap-major) so that a lane's 4 channels are one 16-B load.
+// Depthwise 3x3 + SiLU and the stem (conv + LN + GELU) in f32 containers: the bodies are glue_core.h's.
+// AMP (xp_set_amp_mode): the rounding points of the mixed-precision class (R16 there).
 // ---------------------------------------------------------------------------------------------
-// Each thread produces a PH x PW = 4 x 4 block of pixels x 4 channels, streaming the PH + 2 input rows of its 6-column window
-// once (36 float4 loads per 16 outputs; a thread per output row re-reads two of its three rows: 72).  0.285 -> 0.244 ms per step.  Every output still
-// accumulates its taps in (kh, kw) order with padded taps skipped — input rows arrive in ascending order, and an input row ih
-// is tap kh = ih - oh + 1 of output row oh — so results are bit-identical to the one-row form.
 #ifndef XP_DW_PW
 #define XP_DW_PW 4
 #endif
@@ -138,139 +133,18 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
 #define XP_DW_PH 4
 #endif
 constexpr int DW_PW = XP_DW_PW, DW_PH = XP_DW_PH;      // (-D overrides: tools/instep_ab.sh)
-__device__ __forceinline__ float ew_r16(float v) { return (float)(_Float16)v; }
-// AMP (xp_set_amp_mode): the convolution's output and the SiLU's output are half tensors under autocast: both rounded to fp16
 template <bool AMP>
 __global__ __launch_bounds__(256) void dwconv3x3_silu_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              float* __restrict__ y, int B, int H, int W, int C) {
-    const int C4 = C >> 2;
-    const int WG = (W + DW_PW - 1) / DW_PW, HG = (H + DW_PH - 1) / DW_PH;
-    const int64_t total = (int64_t)B * HG * WG * C4;
-    // XCD-aware block order (workgroup ids go round-robin to the 8 XCDs, one L2 each): every XCD takes one contiguous run of blocks = a band of
-    // image rows, so the halo rows that vertically adjacent blocks share are fetched once per band, not once per block (144 -> MB per launch mix)
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, q = nb >> 3, r = nb & 7;
-    const unsigned blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    const int64_t idx = (int64_t)blk * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int c4 = (int)(idx % C4);
-    const int64_t g = idx / C4;
-    const int w0 = (int)(g % WG) * DW_PW;
-    const int h0 = (int)((g / WG) % HG) * DW_PH;
-    const int64_t b = g / ((int64_t)WG * HG);
-    const float4* xv = reinterpret_cast<const float4*>(x);
-    float4 wt[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) wt[t] = reinterpret_cast<const float4*>(w)[t * C4 + c4];
-    float4 acc[DW_PH][DW_PW];
-#pragma unroll
-    for (int r = 0; r < DW_PH; ++r)
-#pragma unroll
-        for (int p = 0; p < DW_PW; ++p) acc[r][p] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int ir = 0; ir < DW_PH + 2; ++ir) {
-        const int ih = h0 + ir - 1;
-        if (ih < 0 || ih >= H) continue;          // zero padding: a skipped row adds nothing (same sum order for the rest)
-        float4 col[DW_PW + 2];
-#pragma unroll
-        for (int cx = 0; cx < DW_PW + 2; ++cx) {
-            const int iw = w0 + cx - 1;
-            col[cx] = (iw >= 0 && iw < W) ? xv[((b * H + ih) * W + iw) * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int r = 0; r < DW_PH; ++r) {
-            const int kh = ir - r;                // this input row is tap kh of output row h0 + r
-            if (kh < 0 || kh > 2) continue;
-#pragma unroll
-            for (int p = 0; p < DW_PW; ++p)
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-                    const int iw = w0 + p + kw - 1;
-                    if (iw < 0 || iw >= W) continue;   // keep the reference's accumulation order: padded taps are skipped, not added as 0
-                    const float4 xin = col[p + kw], wv = wt[kh * 3 + kw];
-                    acc[r][p].x = fmaf(xin.x, wv.x, acc[r][p].x); acc[r][p].y = fmaf(xin.y, wv.y, acc[r][p].y);
-                    acc[r][p].z = fmaf(xin.z, wv.z, acc[r][p].z); acc[r][p].w = fmaf(xin.w, wv.w, acc[r][p].w);
-                }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < DW_PH; ++r) {
-        if (h0 + r >= H) break;
-#pragma unroll
-        for (int p = 0; p < DW_PW; ++p) {
-            if (w0 + p >= W) break;
-            float4 o = acc[r][p];
-            if (AMP) { o.x = ew_r16(o.x); o.y = ew_r16(o.y); o.z = ew_r16(o.z); o.w = ew_r16(o.w); }
-            o.x = xp_silu(o.x); o.y = xp_silu(o.y); o.z = xp_silu(o.z); o.w = xp_silu(o.w);
-            if (AMP) { o.x = ew_r16(o.x); o.y = ew_r16(o.y); o.z = ew_r16(o.z); o.w = ew_r16(o.w); }
-            reinterpret_cast<float4*>(y)[((b * H + h0 + r) * W + w0 + p) * C4 + c4] = o;
-        }
-    }
+    xp_dwconv3x3_silu_body<float, AMP, false, DW_PH, DW_PW>(x, w, y, nullptr, B, H, W, C, blockDim.x);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Stem: gray image (B,1,H,W) -> conv3x3 stride 2 pad 1 (1 -> CO channels; the reference replicates gray
-// to 3 channels, VMamba.py:1509-1510, so the 3 input-channel weights are pre-summed on the host)
-// + bias + LayerNorm(CO) + GELU -> NHWC (B,H/2,W/2,CO).  Reference VMamba.py:1411-1416.
-// One thread per output pixel, CO accumulators in registers; output staged through LDS for coalescing.
-// ---------------------------------------------------------------------------------------------
-// AMP: the image is cast to half by autocast's convolution, and conv, LayerNorm and GELU each return a half tensor
 template <int CO, bool AMP>
 __global__ __launch_bounds__(64) void stem_conv_ln_gelu_kernel(const float* __restrict__ img, const float* __restrict__ w9,
                                                                const float* __restrict__ bias, const float* __restrict__ lnw,
                                                                const float* __restrict__ lnb, float* __restrict__ y,
                                                                int B, int H, int W, float eps) {
-    __shared__ float s_w[9 * CO + 3 * CO];
-    __shared__ float s_o[64 * (CO + 1)];
-    for (int i = threadIdx.x; i < 9 * CO; i += 64) s_w[i] = w9[i];          // [tap][CO]
-    for (int i = threadIdx.x; i < CO; i += 64) { s_w[9 * CO + i] = bias[i]; s_w[10 * CO + i] = lnw[i]; s_w[11 * CO + i] = lnb[i]; }
-    __syncthreads();
-    const int Ho = H / 2 + (H & 1), Wo = W / 2 + (W & 1);   // floor((H+2-3)/2)+1
-    const int64_t total = (int64_t)B * Ho * Wo;
-    const int64_t p0 = (int64_t)blockIdx.x * 64;
-    const int64_t pix = p0 + threadIdx.x;
-    if (pix < total) {
-        const int ow = (int)(pix % Wo), oh = (int)((pix / Wo) % Ho);
-        const int64_t b = pix / ((int64_t)Wo * Ho);
-        float xin[9];
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
-                xin[kh * 3 + kw] = (ih >= 0 && ih < H && iw >= 0 && iw < W) ? img[(b * H + ih) * W + iw] : 0.f;
-                if (AMP) xin[kh * 3 + kw] = ew_r16(xin[kh * 3 + kw]);
-            }
-        float acc[CO];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < CO; ++c) {
-            float a = 0.f;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) a = fmaf(xin[t], s_w[t * CO + c], a);
-            a += s_w[9 * CO + c];
-            if (AMP) a = ew_r16(a);
-            acc[c] = a; s += a;
-        }
-        const float mean = s / (float)CO;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < CO; ++c) { const float d = acc[c] - mean; q = fmaf(d, d, q); }
-        const float rstd = 1.f / sqrtf(q / (float)CO + eps);
-#pragma unroll
-        for (int c = 0; c < CO; ++c) {
-            float v = (acc[c] - mean) * rstd * s_w[10 * CO + c] + s_w[11 * CO + c];
-            if (AMP) v = ew_r16(v);
-            v = xp_gelu_fast(v);
-            if (AMP) v = ew_r16(v);
-            s_o[threadIdx.x * (CO + 1) + c] = v;
-        }
-    }
-    __syncthreads();
-    const int64_t nvalid = (total - p0 < 64) ? (total - p0) : 64;
-    for (int i = threadIdx.x; i < nvalid * CO; i += 64) {
-        const int pl = i / CO, c = i - pl * CO;
-        y[(p0 + pl) * CO + c] = s_o[pl * (CO + 1) + c];
-    }
+    xp_stem_conv_ln_gelu_body<CO, float, AMP>(img, w9, bias, lnw, lnb, y, B, H, W, eps);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -297,23 +171,10 @@ __global__ __launch_bounds__(256) void depth_to_space_kernel(const float* __rest
     y[((n * (H * bs) + (h * bs + i)) * (int64_t)(W * bs) + (w * bs + j)) * Cq + c] = x[idx];
 }
 
-// float4 form (Cq % 4 == 0, 16-byte aligned buffers, < 2^31 elements): a thread moves four channels of one block — 32-bit index arithmetic, 16-byte accesses
+// float4 form (Cq % 4 == 0, 16-byte aligned buffers, < 2^31 elements): glue_core.h
 __global__ __launch_bounds__(256) void depth_to_space_vec_kernel(const float4* __restrict__ x, float4* __restrict__ y,
                                                                  int B, int H, int W, int C4, int bs, float limit, int* __restrict__ status) {
-    const int Cq4 = C4 / (bs * bs);
-    const unsigned total = (unsigned)B * H * W * C4;
-    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const float4 v = idx < total ? x[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (status) {
-        const bool bad = !(fabsf(v.x) < limit) || !(fabsf(v.y) < limit) || !(fabsf(v.z) < limit) || !(fabsf(v.w) < limit);        // NaN compares false
-        if (__ballot(bad && idx < total) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, XP_STATUS_ENC);
-    }
-    if (idx >= total) return;
-    const unsigned ch = idx % (unsigned)C4, pix = idx / (unsigned)C4;
-    const unsigned w = pix % (unsigned)W, hn = pix / (unsigned)W, h = hn % (unsigned)H, n = hn / (unsigned)H;
-    const unsigned blk = ch / (unsigned)Cq4, c = ch - blk * Cq4;
-    const unsigned i = blk / (unsigned)bs, j = blk - i * bs;
-    y[((n * (H * bs) + (h * bs + i)) * (unsigned)(W * bs) + (w * bs + j)) * Cq4 + c] = v;
+    xp_depth_to_space_vec_body<float>(x, y, nullptr, B, H, W, C4, bs, limit, status, blockDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -456,10 +317,10 @@ __global__ __launch_bounds__(256) void round_f16_kernel(const float* __restrict_
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i + 3 < n) {
         float4 v = *reinterpret_cast<const float4*>(x + i);
-        v.x = ew_r16(v.x); v.y = ew_r16(v.y); v.z = ew_r16(v.z); v.w = ew_r16(v.w);
+        v.x = xp_r16(v.x); v.y = xp_r16(v.y); v.z = xp_r16(v.z); v.w = xp_r16(v.w);
         *reinterpret_cast<float4*>(y + i) = v;
     } else {
-        for (int64_t j = i; j < n; ++j) y[j] = ew_r16(x[j]);
+        for (int64_t j = i; j < n; ++j) y[j] = xp_r16(x[j]);
     }
 }
 extern "C" int xp_round_f16(const float* x, float* y, int64_t n, void* stream) {

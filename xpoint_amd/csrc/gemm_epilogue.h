@@ -37,8 +37,6 @@ struct GemmParams {
 template <class T, class = void> struct tile_has_row_scale : std::false_type {};
 template <class T> struct tile_has_row_scale<T, std::enable_if_t<T::kRowScale>> : std::true_type {};
 
-__device__ __forceinline__ float xp_r16(float v) { return (float)(_Float16)v; }       // round to nearest even to fp16 and back (v_cvt_f16_f32, v_cvt_f32_f16)
-
 // T: tile engine providing BM, BN, row_of(i, r), col_of(j).  acc[i][j] are the lane's 32x32 accumulator tiles.
 // ALLOW_R16: also instantiate the p.r16 form (the split-fp16 kernels; the other engines never set it).
 template <class T, int TM, int TN, bool ALLOW_R16 = false>

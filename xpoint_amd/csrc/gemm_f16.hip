@@ -41,8 +41,6 @@ struct F16Params {
 
 __device__ __attribute__((aligned(64))) unsigned int g_f16_zero_page[16];      // zero-initialised: the source of every out-of-range 16-byte piece
 
-__device__ __forceinline__ float f16_r(float v) { return (float)(_Float16)v; }
-
 template <int WM, int WN, int TM, int TN, int BK>
 struct F16Tile {
     static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64, NW = WM * WN;
@@ -207,10 +205,10 @@ __global__ __launch_bounds__(WM * WN * 64, (BK == 64 ? 2 : 4) / (WM * WN > 4 ? 2
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int rl = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                    float v = f16_r(acc[i][j][r] + bi);                       // the layer's half output (f32 accumulate + bias, one rounding)
-                    if (ACT == 1) v = f16_r(xp_gelu_fast(v));
+                    float v = xp_r16(acc[i][j][r] + bi);                       // the layer's half output (f32 accumulate + bias, one rounding)
+                    if (ACT == 1) v = xp_r16(xp_gelu_fast(v));
                     if (ACT == 2) v = fmaxf(v, 0.f);
-                    if (p.scale) v = f16_r(v * sc + sh);                      // eval BatchNorm on a half tensor returns a half tensor
+                    if (p.scale) v = xp_r16(v * sc + sh);                      // eval BatchNorm on a half tensor returns a half tensor
                     if (ACT == 3) v = fmaxf(v, 0.f);
                     // rows r and r + 4 (the two lane halves) sit 4 rows apart: XOR bit 6 of the byte offset with bit 2 of the row so they use different banks
                     const int off = rl * RS + ((cl * 2) ^ (RS % 128 == 0 ? ((rl >> 2) & 1) << 6 : 0));

@@ -36,7 +36,6 @@ typedef __attribute__((address_space(3))) void* m16_lds_ptr_t;
 namespace {
 
 __device__ __attribute__((aligned(64))) unsigned int g_m16_zero_page[16];
-__device__ __forceinline__ float m16_r(float v) { return (float)(_Float16)v; }
 
 struct Mlp16Params {
     const _Float16* A;      // (M, C)  LayerNorm(x)
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(256, C <= 96 ? XP_MLP16_WG96 : XP_MLP16_WG192) void
                 const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
                 union { _Float16 h[4]; uint2 u; } pk;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) pk.h[q] = (XP_MLP16_DBG & 1) ? (_Float16)(hT[jh][4 * g4 + q] + bv[q]) : (_Float16)xp_gelu_fast(m16_r(hT[jh][4 * g4 + q] + bv[q]));
+                for (int q = 0; q < 4; ++q) pk.h[q] = (XP_MLP16_DBG & 1) ? (_Float16)(hT[jh][4 * g4 + q] + bv[q]) : (_Float16)xp_gelu_fast(xp_r16(hT[jh][4 * g4 + q] + bv[q]));
                 *reinterpret_cast<uint2*>(h_tile + fr * (SPH * 16) + hid0 * 2) = pk.u;
             }
         // ---- fc2: acc2[jn] += H . W2chunk^T ----

@@ -57,8 +57,6 @@ struct RingParams {
     int ngroup;                          // column tiles per group of the tile order (0: all column tiles of a row tile adjacent)
 };
 
-__device__ __forceinline__ float rg_r16(float v) { return (float)(_Float16)v; }
-
 // GM x GN waves per group, TM x TN MFMA tiles (32 x 32) per wave, S ring stages
 template <int GM, int GN, int TM, int TN, int PLANES, int S>
 struct RingTile {
@@ -279,14 +277,14 @@ __global__ __launch_bounds__(512) void ring_gemm_kernel(RingParams p) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     float x = p.wscale ? v[e] * wsv[e] + biv[e] : v[e] + biv[e];          // wscale is a power of two: the product is exact
-                    if (R16) x = rg_r16(x);
-                    if (ACT == 1) { x = xp_gelu_fast(x); if (R16) x = rg_r16(x); }
+                    if (R16) x = xp_r16(x);
+                    if (ACT == 1) { x = xp_gelu_fast(x); if (R16) x = xp_r16(x); }
                     if (ACT == 2) x = fmaxf(x, 0.f);
                     if (!R16 || p.scale) x = x * scv[e] + shv[e];
-                    if (R16) { if (p.scale) x = rg_r16(x); }
+                    if (R16) { if (p.scale) x = xp_r16(x); }
                     if (ACT == 3) x = fmaxf(x, 0.f);
                     if (!R16 || p.res) x = rv[e] + x;                                     // (the f32 classes add the 0 of an absent residual, like gemm_epilogue.h: -0 -> +0)
-                    if (R16) { if (p.res) x = rg_r16(x); }
+                    if (R16) { if (p.res) x = xp_r16(x); }
                     v[e] = x;
                 }
                 if (!ok || (XP_RING_DBG & 8)) continue;

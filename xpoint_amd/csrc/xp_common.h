@@ -93,6 +93,8 @@ unsigned long long xp_dense_override_value();
 int xp_amp_value();
 
 #ifdef __HIPCC__
+// round to nearest even to fp16 and back (v_cvt_f16_f32, v_cvt_f32_f16): the rounding point of the mixed-precision classes
+__device__ __forceinline__ float xp_r16(float v) { return (float)(_Float16)v; }
 // softplus with torch semantics (beta 1, threshold 20): reference csms6s.py:49-50 /
 // selective_scan_fwd_kernel_oflex.cuh:124-127.
 __device__ __forceinline__ float xp_softplus(float x) { return x <= 20.f ? log1pf(expf(x)) : x; }
