@@ -656,6 +656,53 @@ int xp_aug_photo_step(const float* src, float* dst, const int* ops, const float*
                       const float* field_speckle, unsigned long long seed, const int* sample_ids, int B, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dense backward of head training (xpoint_amd/training.py drives these; csrc/train_dense.hip; reference call sites
+ * XPoint.py:112-138 head convolutions and BatchNorms in training mode, :366 F.normalize).  All matrices are f32 rows with a leading dimension.
+ *
+ * xp_gemm_tn_h2: out[i][j] = sum_m P[m][i] Q[m][j] — the weight gradient of a linear layer.  P (M, I) rows with ldp is the GRADIENT operand,
+ * Q (M, J) rows with ldq the activation (a column slice of a wider matrix is passed as the slice's first column and the wide ld); out (I, J)
+ * rows with ldo; nothing outside that window is written.  f32-grade: both operands are split into two fp16 planes, three products per multiply
+ * on the f16 matrix pipe (csrc/gemm_h2_core.h).  P is multiplied by one power of two S per call, taken on the device from its largest magnitude
+ * (max|P| S in [2^13, 2^14)), and the result by 1 / S: exact, any finite range of P is accepted, an all-zero P gives exact zeros; |Q| < 65504.
+ * Non-finite elements of P take no part in the choice of S (the maximum is over the finite part; an infinite maximum gives S = 1) and pass through the
+ * split as they are: every output they touch is NaN / Inf, nothing is hidden.
+ * p_scale NULL: S is found here.  p_scale != NULL: a device float[2] = {S, 1 / S} and P ALREADY holds S x the gradient (xp_bn_train_bwd writes both).
+ * M is cut into chunks of XP_WGRAD_CHUNK rows — a constant of the build, independent of the shape and the device; the chunks' partial results go to
+ * the workspace and are added in chunk order: no atomics, two calls are bit-identical.  Workspace: xp_gemm_tn_h2_workspace_bytes(M, I, J) =
+ * 4352 + ceil(M / XP_WGRAD_CHUNK) I J 4 bytes, 256-byte aligned.
+ * xp_conv3x3_wgrad_h2: the same with Q = the im2col view of the NHWC input x (batch, H, W, Ci) under reflection padding 1, stride 1 (columns in
+ * (ky, kx, ci) order), P = dy (batch H W, Co): dw (Co, 3, 3, Ci), bit-equal to xp_gemm_tn_h2 on the materialised im2col matrix.  Any other
+ * stride / reflect_pad is refused.  Workspace: xp_gemm_tn_h2_workspace_bytes(batch H W, Co, 9 Ci).  No input gradient is built. */
+#define XP_WGRAD_CHUNK 256
+size_t xp_gemm_tn_h2_workspace_bytes(int M, int I, int J);
+int xp_gemm_tn_h2(const float* P, const float* Q, float* out, int M, int I, int J, int ldp, int ldq, int ldo, const float* p_scale,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int xp_conv3x3_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, int stride, int reflect_pad,
+                        const float* dy_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* BatchNorm in training mode over (rows, C) NHWC rows (nn.BatchNorm2d, XPoint.py:64-72,120,136).  Channel sums run in a fixed order with f64
+ * accumulators (64 row groups of 8 lanes each, added in lane and group order; the statistics on data shifted by the channel's first element):
+ * bit-identical between calls.  Workspace for all three entry points below: xp_bn_workspace_bytes(C), 256-byte aligned.
+ * xp_bn_train_fwd: save_mean (2, C) = the f32 mean and the f32 remainder of the f64 mean (x - mean is formed from both, which keeps the data's
+ *   precision when |mean| >> the deviation; row 0 is what the running statistics take), save_invstd (C) = 1 / sqrt(biased var + eps), batch_var (C)
+ *   (biased; may be NULL), y = (x - mean) invstd gamma + beta.  rows >= 2.
+ * xp_bn_train_bwd: dgamma = sum dy xhat, dbeta = sum dy (either may be NULL), dx = gamma invstd (dy - dbeta / rows - xhat dgamma / rows).
+ *   relu_mask != 0: dx is multiplied by [x > 0] — the trunk's order is conv -> ReLU -> BatchNorm, so x is the ReLU's output and dx the gradient of
+ *   the convolution's output.  dx_scale != NULL: a device float[2] that receives {S, 1 / S} with max|dx| S in [2^13, 2^14), and dx is written as
+ *   S x the gradient: the operand format xp_gemm_tn_h2 (p_scale) and xp_gemm_nt_h2 (1 / S in the epilogue's scale vector) read next.
+ * xp_colsum_rows: out[c] = sum_r x[r][c] by the same reduction (the bias gradients); x_scale != NULL: the sum is multiplied by x_scale[1]. */
+size_t xp_bn_workspace_bytes(int C);
+int xp_bn_train_fwd(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* save_mean, float* save_invstd,
+                    float* batch_var, int64_t rows, int C, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int xp_bn_train_bwd(const float* dy, int lddy, const float* x, int ldx, const float* gamma, const float* save_mean /* (2, C) */, const float* save_invstd,
+                    float* dx, int lddx, float* dgamma, float* dbeta, float* dx_scale, int relu_mask, int64_t rows, int C, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int xp_colsum_rows(const float* x, int ldx, int64_t rows, int C, const float* x_scale, float* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* Backward of xp_l2norm_rows (y = x / max(|x|, eps)): dx = (dy - y <dy, y>) / |x| for |x| >= eps, dy / eps below (torch's F.normalize: the
+ * clamp passes no gradient to the norm).  x (rows, C) with ldx is the forward's INPUT; dy, dx (rows, C) contiguous. */
+int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, float* dx, int64_t rows, int C, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -124,6 +124,12 @@ _SIGNATURES = {
     "xp_aug_photo_prologue": [c_p] * 4 + [c_i] * 4 + [c_p],
     "xp_aug_blur": [c_p] * 4 + [c_i] * 5 + [c_p],
     "xp_aug_photo_step": [c_p] * 4 + [c_i, c_i] + [c_p] * 6 + [ctypes.c_uint64, c_p] + [c_i] * 3 + [c_p],
+    "xp_gemm_tn_h2": [c_p] * 3 + [c_i] * 6 + [c_p, c_p, c_sz, c_p],
+    "xp_conv3x3_wgrad_h2": [c_p] * 3 + [c_i] * 7 + [c_p, c_p, c_sz, c_p],
+    "xp_bn_train_fwd": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_l, c_i, c_f, c_p, c_sz, c_p],
+    "xp_bn_train_bwd": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_sz, c_p],
+    "xp_colsum_rows": [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_sz, c_p],
+    "xp_l2norm_rows_bwd": [c_p, c_i, c_p, c_p, c_l, c_i, c_f, c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -164,6 +170,8 @@ _SIZE_QUERIES = {
     "xp_match_cand_cap": (c_i, []),
     "xp_extract_keypoints_workspace_bytes": (c_sz, [c_i] * 3),
     "xp_aug_partials_per_sample": (c_i, [c_i] * 2),
+    "xp_gemm_tn_h2_workspace_bytes": (c_sz, [c_i] * 3),
+    "xp_bn_workspace_bytes": (c_sz, [c_i]),
 }
 
 
