@@ -410,13 +410,18 @@ int xp_xpoint_forward_ex(void* ctx, const float* weights, const void* wsplit, co
  *   (1024 x 1024) are finished band by band and the finisher launch is repeated — launches past convergence exit at once.
  *   max_sweeps_async == 0: synchronous like the reference (returns a finished tensor; banded images: XP_ERR_STATE if bands are still
  *   undecided after all counter slots); > 0: stream-ordered, at most that many finisher launches for banded images, no host
- *   synchronisation — verify later with xp_box_nms_check (0 undecided = exact result; one-band images always are).  Box sizes the
- *   fixed-point form does not cover fall back to tile sweeps with the same two modes. */
+ *   synchronisation — verify later with xp_box_nms_check (0 undecided = exact result; one-band images always are).  Shapes the
+ *   fixed-point form does not cover (fewer than 32 or more than 2048 columns, more than 32 bands) take tile sweeps with the same two
+ *   modes; xp_box_nms_plan tells which form a shape takes. */
 size_t xp_box_nms_workspace_bytes(int batch, int H, int W, int cap);
 int xp_box_nms(const float* prob, float* out, void* workspace, size_t workspace_bytes, int batch, int H, int W,
                float size, float min_prob, float iou, int keep_top_k, int cap, int max_sweeps_async,
                int* converged_host, void* stream);
 int xp_box_nms_check(const void* workspace, int batch, int H, int W, int* undecided_tiles, void* stream);
+/* Which form xp_box_nms takes for (H, W, size, iou), computed by the launcher's own functions; host only, no launch, no device.
+ * plan[0..4] = form (0 tile sweeps, 1 local maxima + finisher), reach (largest |dy|, |dx| at which two boxes overlap with IoU > iou),
+ * bands per image, rows per band, undecided candidates per band whose list fits LDS (more go to the workspace). */
+int xp_box_nms_plan(int H, int W, float size, float iou, int* plan);
 
 /* torch.nonzero((prob > thr) [* mask]) per image (predict_align_image_pair.py:242-243, predict_keypoints.py:213-215):
  * kp (batch, cap, 2) int32 (y, x) in row-major order, counts (batch) int32 (may exceed cap: truncated list). */

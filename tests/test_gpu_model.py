@@ -439,7 +439,7 @@ def test_pipeline_edge_cases(gpu_lib):
 
 
 def test_async_nms_reports_non_convergence(gpu_lib):
-    """Forms of xp_box_nms.  An image whose bit masks fit one workgroup's LDS (every model size up to ~1000 x 700) is ONE band: local maxima, one
+    """Forms of xp_box_nms.  An image whose bit masks fit one workgroup's LDS (480 x 640; 1000 x 700 is already two: tests/test_cpu_postproc_plan.py) is ONE band: local maxima, one
     suppression pass, then a per-image finisher that iterates to the fixed point INSIDE its launch — no sweep count, always converged, also on a
     640-long suppression chain.  Larger images are split into row bands whose finishers see their neighbours as the launch found them; a chain that
     crosses band borders needs one launch per border: the stream-ordered mode enqueues a fixed number and reports what is left, the synchronous mode

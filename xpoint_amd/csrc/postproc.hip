@@ -158,7 +158,9 @@ __global__ __launch_bounds__(256) void nms_sweep_kernel(const float* __restrict_
 //      round-1 keeper suppresses, ranks what is left (row-major rank = row base + word prefix + popcount) into a score table in LDS and runs
 //      the keep / suppress fixed point as Jacobi rounds separated by workgroup barriers until nothing is undecided — no other workgroup, no
 //      host round trip, no sweep count.  Later keepers patch the output sparsely.
-// Images whose masks do not fit LDS (1024 x 1024) keep the sweep form above.
+// Images whose masks do not fit LDS as one band (1024 x 1024: 3 bands, 2048 x 640: 4) are finished band by band, the finisher launch repeated.
+// The sweep form above is left with images narrower than 32 columns, wider than 64 mask words or taller than 32 bands (nms_two_launch_applies;
+// xp_box_nms_plan tells).
 // ---------------------------------------------------------------------------------------------
 #ifndef XP_NMS_DBG
 #define XP_NMS_DBG 0   /* timing experiments only (wrong results), nms_localmax_kernel: 1 no candidate tests, 2 no out store, 4 no list building, 8 no loads, 16 no window walk */
@@ -492,7 +494,8 @@ __global__ __launch_bounds__(NMS_FIN_THREADS) void nms_finish_kernel(const float
     int my_base = my_count ? atomicAdd(&s_n, my_count) : 0;
     __syncthreads();
     const int total = s_n;
-    const int cap = total <= pl.list_cap ? pl.list_cap : pl.brows * W;
+    // (workspace: positions then scores, sized by the rows this band OWNS — with pl.brows a short last band's scores would run past the image's slice)
+    const int cap = total <= pl.list_cap ? pl.list_cap : (yb1 - yb0) * W;
     int* list = total <= pl.list_cap ? reinterpret_cast<int*>(fin_lds + pl.list_off) : glist + ((int64_t)b * H + yb0) * W * 2;
     float* lscore = reinterpret_cast<float*>(list + cap);
     for (int i = tid; i < nwords; i += NMS_FIN_THREADS) {
@@ -925,6 +928,22 @@ bool nms_two_launch_applies(int H, int W, int R) {
 extern "C" size_t xp_box_nms_workspace_bytes(int batch, int H, int W, int cap) {
     // state bytes (sweep form) / bit masks (two-launch form) + tile flags + counters + (top-k) keypoint list, counts, ranks + score-table overflow + info
     return nms_ws_tail_offset(batch, H, W, cap) + 2 * sizeof(float) * (size_t)batch * H * W + sizeof(int) * (8 * (size_t)batch + 64);
+}
+
+// Which form xp_box_nms takes for a shape and box, from the launcher's own functions (host only: no launch, no device).
+// plan[0..4] = form (0 sweep, 1 two-launch), reach, bands, rows per band, list_cap (undecided candidates whose list fits LDS).
+extern "C" int xp_box_nms_plan(int H, int W, float size, float iou, int* plan) {
+    XP_CHECK_ARG(plan, "xp_box_nms_plan: null pointer");
+    XP_CHECK_ARG(H > 0 && W > 0, "xp_box_nms_plan: bad shape");
+    NmsTable tab;
+    XP_CHECK_ARG(make_nms_table(size, iou, &tab), "xp_box_nms: size must be a positive multiple of 0.5 and <= %d (got %f)", NMS_MAXR + 1, size);
+    const NmsFinishPlan pl = nms_finish_plan(H, W, tab.reach, NMS_FIN_LDS);
+    plan[0] = nms_two_launch_applies(H, W, tab.reach) ? 1 : 0;
+    plan[1] = tab.reach;
+    plan[2] = pl.bands;
+    plan[3] = pl.brows;
+    plan[4] = pl.list_cap;
+    return XP_OK;
 }
 
 // Enqueue `sweeps` sweep launches (each exits at once when the previous one left nothing undecided).
