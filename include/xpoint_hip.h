@@ -677,7 +677,8 @@ int xp_aug_photo_step(const float* src, float* dst, const int* ops, const float*
  * 4352 + ceil(M / XP_WGRAD_CHUNK) I J 4 bytes, 256-byte aligned.
  * xp_conv3x3_wgrad_h2: the same with Q = the im2col view of the NHWC input x (batch, H, W, Ci) under reflection padding 1, stride 1 (columns in
  * (ky, kx, ci) order), P = dy (batch H W, Co): dw (Co, 3, 3, Ci), bit-equal to xp_gemm_tn_h2 on the materialised im2col matrix.  Any other
- * stride / reflect_pad is refused.  Workspace: xp_gemm_tn_h2_workspace_bytes(batch H W, Co, 9 Ci).  No input gradient is built. */
+ * stride / reflect_pad is refused.  Workspace: xp_gemm_tn_h2_workspace_bytes(batch H W, Co, 9 Ci).  No input gradient is built for the reflection-padded
+ * convolution (the zero-padded one has xp_conv3x3_dgrad_h2, below). */
 #define XP_WGRAD_CHUNK 256
 size_t xp_gemm_tn_h2_workspace_bytes(int M, int I, int J);
 int xp_gemm_tn_h2(const float* P, const float* Q, float* out, int M, int I, int J, int ldp, int ldq, int ldo, const float* p_scale,
@@ -706,6 +707,44 @@ int xp_colsum_rows(const float* x, int ldx, int64_t rows, int C, const float* x_
 /* Backward of xp_l2norm_rows (y = x / max(|x|, eps)): dx = (dy - y <dy, y>) / |x| for |x| >= eps, dy / eps below (torch's F.normalize: the
  * clamp passes no gradient to the norm).  x (rows, C) with ldx is the forward's INPUT; dy, dx (rows, C) contiguous. */
 int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, float* dx, int64_t rows, int C, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training of the homography head (xpoint_amd/training.py RegNetHead; csrc/train_dense.hip, csrc/train_regnet.hip; reference
+ * xpoint/models/RegNet.py:12-42 in training mode).  The head's layers are conv3x3 (ZERO padding 1, stride 1, no bias) -> BatchNorm -> ReLU, so the
+ * ReLU gates below read the BatchNorm output and xp_bn_train_bwd runs with relu_mask = 0.
+ *
+ * xp_conv3x3_zp_wgrad_h2: dw (Co, 3, 3, Ci) of the zero-padded convolution, x (batch, H, W, Ci), dy (batch, H, W, Co).  The kernel, chunking
+ *   (XP_WGRAD_CHUNK), scale contract (dy_scale NULL or {S, 1 / S}) and workspace (xp_gemm_tn_h2_workspace_bytes of (batch H W, Co, 9 Ci)) of
+ *   xp_conv3x3_wgrad_h2; a tap outside the image contributes 0.  Bit-equal to xp_gemm_tn_h2 on the materialised zero-padded im2col.  H, W >= 1.
+ * xp_conv3x3_dgrad_h2: the input gradient dx (batch, H, W, Ci) of the same convolution from dy (batch, H, W, Co) and w (Co, 3, 3, Ci) — the forward
+ *   zero-padded convolution of dy with wr[ci][ky][kx][co] = w[co][2 - ky][2 - kx][ci] on the engine of xp_conv3x3_nhwc_h2 (f32-grade, no atomics, two
+ *   calls bit-identical).  dy_scale != NULL: a device float[2] {S, 1 / S} and dy ALREADY holds S x the gradient (what xp_bn_train_bwd writes);
+ *   NULL: S is taken here from the largest magnitude of dy (max|dy| S in [2^13, 2^14)) and a scaled copy in the workspace is what the engine reads,
+ *   so any finite gradient range is accepted.  dx is the UNSCALED gradient (1 / S is applied, exactly, by the epilogue).  Co % 4 == 0 (the engine
+ *   loads dy in 4-element channel groups); |w| is unrestricted (row scales of the offline split).  Workspace:
+ *   xp_conv3x3_dgrad_h2_workspace_bytes, 256-byte aligned.  Reflection-padded and stride-2 convolutions get no input gradient in this build.
+ * xp_relu_fwd: y = max(x, 0) over n elements.  xp_relu_bwd: dy = dr where y > 0, else 0 (y the ReLU's input or its output).
+ * xp_maxpool2_relu_bwd: backward of MaxPool2d(2) over ReLU(y), y (batch, H, W, C) the BatchNorm output, dpool (batch, H / 2, W / 2, C):
+ *   dy = dpool of the window at the FIRST position, in row-major order inside the window, that attains the window's maximum, provided the maximum is
+ *   > 0; 0 everywhere else, the trailing row / column of an odd H / W included (MaxPool2d floors).  torch's choice element for element: ties at 0 are
+ *   closed by the ReLU, positive ties go to the first index.
+ * xp_costvolume_mean_bwd: backward of xp_costvolume_mean: da[n][p][:] = dv[n][p] m[n][:] with m = mean_q b[n][q], db[n][q][:] =
+ *   (sum_p dv[n][p] a[n][p][:]) / hw for every q; the sums over positions run in ascending order.  a, b, da, db (batch, hw, C), dv (batch, hw); C <= 4096.
+ * xp_dropout_rows: y = x keep / (1 - p) over (rows, C) rows.  use_mask == 0: keep[r][c] = [u >= p] with u the first word of the Philox4x32-10 of
+ *   csrc/philox.h (the augmentation's generator) keyed by (seed, sample_ids[r], tag) with counter c, as (word >> 8) 2^-24 — a sample's mask does
+ *   not depend on its batch neighbours; mask (u8, may be NULL) receives keep.  use_mask != 0: the given mask is applied (the backward pass, and
+ *   replaying recorded masks).  0 <= p < 1, 0 <= tag < 8, rows <= 65535. */
+int xp_conv3x3_zp_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_conv3x3_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co);
+int xp_conv3x3_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int xp_relu_fwd(const float* x, float* y, int64_t n, void* stream);
+int xp_relu_bwd(const float* dr, const float* y, float* dy, int64_t n, void* stream);
+int xp_maxpool2_relu_bwd(const float* dpool, const float* y, float* dy, int batch, int H, int W, int C, void* stream);
+int xp_costvolume_mean_bwd(const float* a, const float* b, const float* dv, float* da, float* db, int batch, int hw, int C, void* stream);
+int xp_dropout_rows(const float* x, float* y, unsigned char* mask /* u8, in or out */, int use_mask, unsigned long long seed, const int* sample_ids,
+                    int tag, float p, int rows, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the

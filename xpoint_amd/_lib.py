@@ -131,6 +131,13 @@ _SIGNATURES = {
     "xp_bn_train_bwd": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_sz, c_p],
     "xp_colsum_rows": [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_sz, c_p],
     "xp_l2norm_rows_bwd": [c_p, c_i, c_p, c_p, c_l, c_i, c_f, c_p],
+    "xp_conv3x3_zp_wgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
+    "xp_conv3x3_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
+    "xp_relu_fwd": [c_p, c_p, c_l, c_p],
+    "xp_relu_bwd": [c_p, c_p, c_p, c_l, c_p],
+    "xp_maxpool2_relu_bwd": [c_p] * 3 + [c_i] * 4 + [c_p],
+    "xp_costvolume_mean_bwd": [c_p] * 5 + [c_i] * 3 + [c_p],
+    "xp_dropout_rows": [c_p, c_p, c_p, c_i, ctypes.c_uint64, c_p, c_i, c_f, c_i, c_i, c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -173,6 +180,7 @@ _SIZE_QUERIES = {
     "xp_aug_partials_per_sample": (c_i, [c_i] * 2),
     "xp_gemm_tn_h2_workspace_bytes": (c_sz, [c_i] * 3),
     "xp_bn_workspace_bytes": (c_sz, [c_i]),
+    "xp_conv3x3_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
 }
 
 

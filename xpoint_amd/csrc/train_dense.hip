@@ -1,5 +1,6 @@
 // Dense backward kernels of head training: the weight-gradient GEMM on the split-fp16 matrix path, its implicit 3x3 form,
-// BatchNorm training forward / backward over NHWC rows, the column sums behind the bias gradients and the L2-normalise backward.
+// BatchNorm training forward / backward over NHWC rows, the column sums behind the bias gradients and the L2-normalise backward; at the end of the
+// file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head.
 //
 // Weight gradient.  out[i][j] = sum_m P[m][i] Q[m][j]: the reduction runs over the SLOW dimension of both operands, so a 32-row slab of each is split
 // into its two fp16 planes (gemm_h2_core.h) in registers and stored to the LDS in the transposed image — tile row = output row / column, 32 k values
@@ -81,7 +82,8 @@ struct WgParams {
 
 __device__ __forceinline__ int td_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-template <bool CONV>
+// CONV: 0 = Q is a matrix, 1 = the im2col view under reflection padding, 2 = under zero padding (a tap outside the image contributes 0)
+template <int CONV>
 __global__ __launch_bounds__(256) void td_wgrad_kernel(const WgParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * WG_BT * H2_ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -118,13 +120,19 @@ __global__ __launch_bounds__(256) void td_wgrad_kernel(const WgParams p) {
                 const float pv = pr[pok[e] ? e : -(4 * cq)];                 // columns past I read the tile's first column, which exists
                 pa[r][e] = (mok && pok[e]) ? pv * mul : 0.f;
                 float qv;
-                if (CONV) {
+                bool tap = true;
+                if (CONV == 1) {
                     const int yy = td_reflect(y + qky[e], p.H), xx = td_reflect(x + qkx[e], p.W);
+                    qv = p.Q[(((int64_t)b * p.H + yy) * p.W + xx) * p.Ci + qci[e]];
+                } else if (CONV == 2) {
+                    const int ty = y + qky[e], tx = x + qkx[e];
+                    tap = ty >= 0 && ty < p.H && tx >= 0 && tx < p.W;
+                    const int yy = min(max(ty, 0), p.H - 1), xx = min(max(tx, 0), p.W - 1);      // a valid address: the load is unconditional, the value is selected
                     qv = p.Q[(((int64_t)b * p.H + yy) * p.W + xx) * p.Ci + qci[e]];
                 } else {
                     qv = p.Q[(int64_t)mc * p.ldq + (qok[e] ? j0 + 4 * cq + e : j0)];
                 }
-                qa[r][e] = (mok && qok[e]) ? qv : 0.f;
+                qa[r][e] = (mok && qok[e] && tap) ? qv : 0.f;
             }
         }
     };
@@ -192,7 +200,7 @@ static size_t td_wgrad_bytes(int M, int I, int J) {
     return (size_t)WG_HEAD_BYTES + (size_t)xp_cdiv(M, WG_CHUNK) * I * J * sizeof(float);
 }
 
-static int td_wgrad_launch(const char* who, bool conv, WgParams p, float* out, int ldo, const float* p_scale, void* ws, size_t ws_bytes, hipStream_t s) {
+static int td_wgrad_launch(const char* who, int conv, WgParams p, float* out, int ldo, const float* p_scale, void* ws, size_t ws_bytes, hipStream_t s) {
     XP_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0 && ws_bytes >= td_wgrad_bytes(p.M, p.I, p.J), "%s: workspace of %zu bytes, 256-byte aligned, needed (got %zu)",
                  who, td_wgrad_bytes(p.M, p.I, p.J), ws_bytes);
     XP_CHECK_ARG((int64_t)p.I * p.J < (1 << 30) && (int64_t)p.M * (int64_t)max(p.ldp, p.ldq) < ((int64_t)1 << 40), "%s: shape too large", who);
@@ -213,9 +221,10 @@ static int td_wgrad_launch(const char* who, bool conv, WgParams p, float* out, i
     const dim3 grid(xp_cdiv(p.J, WG_BT), xp_cdiv(p.I, WG_BT), nchunk);
     XP_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "%s: shape too large", who);
     {
-        XpProfScope prof(conv ? "conv3x3_wgrad_h2" : "gemm_tn_h2", s, 6.0 * p.M * p.I * p.J, 4.0 * p.M * (p.I + p.J));
-        if (conv) hipLaunchKernelGGL(td_wgrad_kernel<true>, grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(td_wgrad_kernel<false>, grid, dim3(256), 0, s, p);
+        XpProfScope prof(conv == 2 ? "conv3x3_zp_wgrad_h2" : conv ? "conv3x3_wgrad_h2" : "gemm_tn_h2", s, 6.0 * p.M * p.I * p.J, 4.0 * p.M * (p.I + p.J));
+        if (conv == 1) hipLaunchKernelGGL(td_wgrad_kernel<1>, grid, dim3(256), 0, s, p);
+        else if (conv == 2) hipLaunchKernelGGL(td_wgrad_kernel<2>, grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(td_wgrad_kernel<0>, grid, dim3(256), 0, s, p);
         XP_LAUNCH_CHECK();
     }
     XpProfScope prof("wgrad_sum", s, 0.0, 4.0 * (nchunk + 1) * p.I * p.J);
@@ -379,7 +388,7 @@ extern "C" int xp_gemm_tn_h2(const float* P, const float* Q, float* out, int M, 
     XP_CHECK_ARG(M > 0 && I > 0 && J > 0 && ldp >= I && ldq >= J && ldo >= J, "xp_gemm_tn_h2: bad shape M=%d I=%d J=%d ldp=%d ldq=%d ldo=%d", M, I, J, ldp, ldq, ldo);
     WgParams p{};
     p.P = P; p.Q = Q; p.M = M; p.I = I; p.J = J; p.ldp = ldp; p.ldq = ldq;
-    return td_wgrad_launch("xp_gemm_tn_h2", false, p, out, ldo, p_scale, workspace, workspace_bytes, (hipStream_t)stream);
+    return td_wgrad_launch("xp_gemm_tn_h2", 0, p, out, ldo, p_scale, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int xp_conv3x3_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, int stride, int reflect_pad,
@@ -391,7 +400,7 @@ extern "C" int xp_conv3x3_wgrad_h2(const float* x, const float* dy, float* dw, i
                  "xp_conv3x3_wgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d (reflection needs H, W >= 2)", batch, H, W, Ci, Co);
     WgParams p{};
     p.P = dy; p.Q = x; p.M = batch * H * W; p.I = Co; p.J = 9 * Ci; p.ldp = Co; p.ldq = 0; p.H = H; p.W = W; p.Ci = Ci;
-    return td_wgrad_launch("xp_conv3x3_wgrad_h2", true, p, dw, 9 * Ci, dy_scale, workspace, workspace_bytes, (hipStream_t)stream);
+    return td_wgrad_launch("xp_conv3x3_wgrad_h2", 1, p, dw, 9 * Ci, dy_scale, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" size_t xp_bn_workspace_bytes(int C) { return td_bn_bytes(C); }
@@ -465,4 +474,92 @@ extern "C" int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, floa
     hipLaunchKernelGGL(td_l2norm_bwd_kernel, dim3(xp_cdiv(rows, 4)), dim3(256), 0, s, x, ldx, dy, dx, rows, C, eps);
     XP_LAUNCH_CHECK();
     return XP_OK;
+}
+
+// ---- the zero-padded 3x3 convolution of the RegNet head (RegNet.py:13-18): weight gradient and input gradient ----
+namespace {
+
+// wr[ci][ky][kx][co] = w[co][2 - ky][2 - kx][ci]: the weight whose FORWARD zero-pad convolution of dy is the input gradient
+__global__ __launch_bounds__(256) void td_rot_weights_kernel(const float* __restrict__ w, float* __restrict__ wr, int Ci, int Co) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Ci * 9 * Co) return;
+    const int co = idx % Co, tap = (idx / Co) % 9, ci = idx / (9 * Co);
+    wr[idx] = w[((int64_t)co * 9 + (8 - tap)) * Ci + ci];
+}
+// the epilogue's affine of the input gradient: scale[c] = 1 / S, shift[c] = 0
+__global__ __launch_bounds__(256) void td_unscale_vec_kernel(const float2* __restrict__ s, float* __restrict__ scale, float* __restrict__ shift, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) { scale[c] = s->y; shift[c] = 0.f; }
+}
+__global__ __launch_bounds__(256) void td_scaled_copy_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int C, const float2* __restrict__ scale) {
+    const float S = scale->x;
+    td_for_each(rows, C, [&](int64_t r, int c) { y[r * C + c] = x[r * C + c] * S; });
+}
+
+static size_t td_up256(size_t n) { return (n + 255) & ~(size_t)255; }
+struct DgradLayout { size_t vec, wrot, wsplit, dys, total; };
+static DgradLayout td_dgrad_layout(int batch, int H, int W, int Ci, int Co) {
+    DgradLayout l{};
+    l.vec = WG_HEAD_BYTES;                                                   // head: partial maxima and {S, 1 / S}, as the weight gradient's
+    l.wrot = l.vec + td_up256((size_t)2 * Ci * sizeof(float));
+    l.wsplit = l.wrot + td_up256((size_t)9 * Ci * Co * sizeof(float));
+    l.dys = l.wsplit + td_up256(xp_split_weights_h2_bytes(Ci, 9 * Co));
+    l.total = l.dys + td_up256((size_t)batch * H * W * Co * sizeof(float));
+    return l;
+}
+static bool td_conv_shape_ok(int batch, int H, int W, int Ci, int Co) {
+    return batch > 0 && H >= 1 && W >= 1 && Ci > 0 && Co > 0 && (int64_t)batch * H * W < ((int64_t)1 << 31) / 16 && (int64_t)Ci * Co < (1 << 26);
+}
+
+}  // namespace
+
+extern "C" int xp_conv3x3_zp_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(x && dy && dw, "xp_conv3x3_zp_wgrad_h2: null pointer");
+    XP_CHECK_ARG(td_conv_shape_ok(batch, H, W, Ci, Co), "xp_conv3x3_zp_wgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d", batch, H, W, Ci, Co);
+    WgParams p{};
+    p.P = dy; p.Q = x; p.M = batch * H * W; p.I = Co; p.J = 9 * Ci; p.ldp = Co; p.ldq = 0; p.H = H; p.W = W; p.Ci = Ci;
+    return td_wgrad_launch("xp_conv3x3_zp_wgrad_h2", 2, p, dw, 9 * Ci, dy_scale, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t xp_conv3x3_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co) {
+    if (!td_conv_shape_ok(batch, H, W, Ci, Co)) return 0;
+    return td_dgrad_layout(batch, H, W, Ci, Co).total;
+}
+
+extern "C" int xp_conv3x3_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(dy && w && dx, "xp_conv3x3_dgrad_h2: null pointer");
+    XP_CHECK_ARG(td_conv_shape_ok(batch, H, W, Ci, Co), "xp_conv3x3_dgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d", batch, H, W, Ci, Co);
+    XP_CHECK_ARG(Co % 4 == 0, "xp_conv3x3_dgrad_h2: Co must be a multiple of 4 (got %d): the engine loads dy in 4-element channel groups", Co);
+    const DgradLayout l = td_dgrad_layout(batch, H, W, Ci, Co);
+    XP_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= l.total,
+                 "xp_conv3x3_dgrad_h2: workspace of %zu bytes, 256-byte aligned, needed (got %zu)", l.total, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* amax = (float*)ws;
+    const float2* scale = (const float2*)dy_scale;
+    float* vscale = (float*)(ws + l.vec);
+    float* vshift = vscale + Ci;
+    float* wrot = (float*)(ws + l.wrot);
+    const int64_t rows = (int64_t)batch * H * W;
+    if (!dy_scale) {          // S from the largest magnitude of dy, and the scaled copy the engine reads
+        float2* own = (float2*)(ws + AMAX_PARTS * 4);
+        float* dys = (float*)(ws + l.dys);
+        const int nb = td_elem_blocks(rows);
+        hipLaunchKernelGGL(td_amax_kernel, dim3(nb), dim3(256), 0, s, dy, rows, Co, Co, amax);
+        XP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(td_scale_kernel, dim3(1), dim3(256), 0, s, amax, nb, own);
+        XP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(td_scaled_copy_kernel, dim3(nb), dim3(256), 0, s, dy, dys, rows, Co, own);
+        XP_LAUNCH_CHECK();
+        scale = own; dy = dys;
+    }
+    hipLaunchKernelGGL(td_unscale_vec_kernel, dim3(xp_cdiv(Ci, 256)), dim3(256), 0, s, scale, vscale, vshift, Ci);
+    XP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(td_rot_weights_kernel, dim3(xp_cdiv(9 * Ci * Co, 256)), dim3(256), 0, s, w, wrot, Ci, Co);
+    XP_LAUNCH_CHECK();
+    XP_TRY(xp_split_weights_h2(wrot, ws + l.wsplit, Ci, 9 * Co, stream));
+    // dx = conv3x3(zero_pad(S dy), wrot) / S on the forward's implicit-GEMM engine: no atomics, the engine's fixed summation order
+    return xp_conv3x3_nhwc_h2(dy, ws + l.wsplit, dx, nullptr, vscale, vshift, batch, H, W, Co, Ci, 1, 0, 0, stream);
 }

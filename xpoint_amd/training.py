@@ -17,7 +17,11 @@ gradients.  There is no CPU fallback and no gradient for the encoder: an `enc_nh
 
 Only the f32-grade class is built (split-fp16 operands, three products): activations must stay below 65504 in magnitude (the encoder output
 and the trunk's BatchNorm output: O(1) in this network); gradients of any finite range are accepted (one power of two per operand).
-Not built: autocast / GradScaler training, the RegNet head's training, a training command line."""
+`RegNetHead` is the homography regression head (reference RegNet.py) behind the same frozen encoder: two zero-padded 3x3 convolutions in the order
+conv -> BatchNorm -> ReLU, max pool, F.normalize, the cost volume's global mean, and two linear layers with dropout.  Its backward adds the zero-padded
+convolution's weight gradient (xp_conv3x3_zp_wgrad_h2) and INPUT gradient (xp_conv3x3_dgrad_h2: the forward engine on the rotated, transposed weight),
+the ReLU / max-pool gates on the BatchNorm output, the cost volume's backward and a counter-based dropout.
+Not built: autocast / GradScaler training, the encoder's gradient, a training command line."""
 from __future__ import annotations
 
 import ctypes
@@ -27,7 +31,8 @@ import torch
 from . import _lib
 from ._lib import ptr
 
-__all__ = ["XPointHeads", "finetune_step", "gemm_tn", "conv3x3_wgrad", "bn_train_fwd", "bn_train_bwd", "colsum_rows", "l2norm_rows_bwd"]
+__all__ = ["XPointHeads", "RegNetHead", "finetune_step", "gemm_tn", "conv3x3_wgrad", "bn_train_fwd", "bn_train_bwd", "colsum_rows", "l2norm_rows_bwd",
+           "conv3x3_wgrad_zero_pad", "conv3x3_dgrad", "relu_bwd", "maxpool2_relu_bwd", "costvolume_mean_bwd", "dropout_rows"]
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -160,6 +165,103 @@ def l2norm_rows_bwd(x, dy, eps=L2_EPS, stream=None):
     dx = torch.empty((rows, C), dtype=torch.float32, device=x.device)
     _lib.call("xp_l2norm_rows_bwd", _vp(x), int(x.stride(0)), ptr(dy), ptr(dx), rows, C, float(eps), _lib.current_stream(x) if stream is None else stream)
     return dx
+
+
+def conv3x3_wgrad_zero_pad(x_nhwc, dy_nhwc, dy_scale=None, stream=None):
+    """Weight gradient (Co, 3, 3, Ci) of the stride-1 3x3 convolution with ZERO padding 1 (the RegNet head's): x (B, H, W, Ci), dy (B, H, W, Co)."""
+    _check_operands("conv3x3_wgrad_zero_pad", x_nhwc, dy_nhwc, dy_scale)
+    if x_nhwc.dim() != 4 or dy_nhwc.dim() != 4 or tuple(dy_nhwc.shape[:3]) != tuple(x_nhwc.shape[:3]):
+        raise ValueError(f"conv3x3_wgrad_zero_pad: x {tuple(x_nhwc.shape)} and dy {tuple(dy_nhwc.shape)} do not share (B, H, W)")
+    B, H, W, Ci = x_nhwc.shape
+    Co = dy_nhwc.shape[-1]
+    dw = torch.empty((Co, 3, 3, Ci), dtype=torch.float32, device=x_nhwc.device)
+    ws = _bytes(_lib.load().xp_gemm_tn_h2_workspace_bytes(B * H * W, Co, 9 * Ci), x_nhwc.device)
+    _lib.call("xp_conv3x3_zp_wgrad_h2", ptr(x_nhwc), ptr(dy_nhwc), ptr(dw), B, H, W, Ci, Co, None if dy_scale is None else _vp(dy_scale), ptr(ws),
+              ctypes.c_size_t(ws.numel()), _lib.current_stream(x_nhwc) if stream is None else stream)
+    return dw
+
+
+def conv3x3_dgrad(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
+    """Input gradient (B, H, W, Ci) of the stride-1 zero-padded 3x3 convolution from dy (B, H, W, Co) and w (Co, 3, 3, Ci).  dy_scale: None, or
+    the device float[2] {S, 1 / S} of a dy that already holds S x the gradient; the result is the unscaled gradient either way.  Co % 4 == 0."""
+    _check_operands("conv3x3_dgrad", dy_nhwc, w_ohwi, dy_scale)
+    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3):
+        raise ValueError(f"conv3x3_dgrad: dy {tuple(dy_nhwc.shape)} must be (B, H, W, Co) and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
+    B, H, W, Co = dy_nhwc.shape
+    Ci = w_ohwi.shape[-1]
+    dx = torch.empty((B, H, W, Ci), dtype=torch.float32, device=dy_nhwc.device)
+    ws = _bytes(_lib.load().xp_conv3x3_dgrad_h2_workspace_bytes(B, H, W, Ci, Co), dy_nhwc.device)
+    _lib.call("xp_conv3x3_dgrad_h2", ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, None if dy_scale is None else _vp(dy_scale), ptr(ws),
+              ctypes.c_size_t(ws.numel()), _lib.current_stream(dy_nhwc) if stream is None else stream)
+    return dx
+
+
+def _relu(x, stream=None):
+    y = torch.empty_like(x)
+    _lib.call("xp_relu_fwd", ptr(x), ptr(y), x.numel(), _lib.current_stream(x) if stream is None else stream)
+    return y
+
+
+def relu_bwd(dr, y, stream=None):
+    """dy = dr where y > 0, else 0 (y: the ReLU's input, or its output)."""
+    _check_operands("relu_bwd", dr, y)
+    if dr.shape != y.shape:
+        raise ValueError("relu_bwd: dr must have the shape of y")
+    dr, y = dr.contiguous(), y.contiguous()
+    dy = torch.empty_like(y)
+    _lib.call("xp_relu_bwd", ptr(dr), ptr(y), ptr(dy), y.numel(), _lib.current_stream(y) if stream is None else stream)
+    return dy
+
+
+def maxpool2_relu_bwd(dpool, y_nhwc, stream=None):
+    """Backward of max_pool2d(relu(y), 2): y (B, H, W, C), dpool (B, H // 2, W // 2, C) -> dy (B, H, W, C), torch's choice element for element."""
+    _check_operands("maxpool2_relu_bwd", dpool, y_nhwc)
+    B, H, W, C = y_nhwc.shape
+    if tuple(dpool.shape) != (B, H // 2, W // 2, C):
+        raise ValueError(f"maxpool2_relu_bwd: dpool {tuple(dpool.shape)} must be {(B, H // 2, W // 2, C)}")
+    dy = torch.empty_like(y_nhwc, memory_format=torch.contiguous_format)
+    _lib.call("xp_maxpool2_relu_bwd", ptr(dpool.contiguous()) if dpool.numel() else None, ptr(y_nhwc), ptr(dy), B, H, W, C,
+              _lib.current_stream(y_nhwc) if stream is None else stream)
+    return dy
+
+
+def costvolume_mean_bwd(a, b, dv, stream=None):
+    """Backward of v[n][p] = a[n][p] . mean_q b[n][q]: a, b (B, hw, C), dv (B, hw) -> (da, db)."""
+    _check_operands("costvolume_mean_bwd", a, b, dv)
+    B, hw, C = a.shape
+    if b.shape != a.shape or tuple(dv.shape) != (B, hw):
+        raise ValueError("costvolume_mean_bwd: b as a (B, hw, C), dv (B, hw)")
+    da, db = torch.empty_like(a, memory_format=torch.contiguous_format), torch.empty_like(a, memory_format=torch.contiguous_format)
+    _lib.call("xp_costvolume_mean_bwd", ptr(a), ptr(b), ptr(dv.contiguous()), ptr(da), ptr(db), B, hw, C, _lib.current_stream(a) if stream is None else stream)
+    return da, db
+
+
+def dropout_rows(x, p=0.5, seed=0, sample_ids=None, tag=0, mask=None, stream=None):
+    """nn.Dropout(p) over the rows of x (rows, C) -> (y, mask (rows, C) uint8).  mask None: row r keeps column c iff the uniform draw of
+    (seed, sample_ids[r], tag, c) is >= p (sample_ids: int32 device tensor, default 0 .. rows - 1), so a sample's mask does not depend on its batch
+    neighbours; mask given: it is applied as it is (the backward pass; replaying recorded masks)."""
+    _check_operands("dropout_rows", x)
+    rows, C = x.shape
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    for t, what in ((mask, "mask"), (sample_ids, "sample_ids")):
+        if t is not None:
+            _need_device(t, "dropout_rows")
+            if t.device != x.device:
+                raise _lib.XPointHipError(f"dropout_rows: x and {what} live on different devices")
+    if mask is not None:
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (rows, C):
+            raise ValueError(f"dropout_rows: mask must be uint8 ({rows}, {C})")
+        mask, use = mask.contiguous(), 1
+        ids = None
+    else:
+        mask, use = torch.empty((rows, C), dtype=torch.uint8, device=x.device), 0
+        ids = torch.arange(rows, dtype=torch.int32, device=x.device) if sample_ids is None else sample_ids.to(torch.int32).contiguous()
+        if tuple(ids.shape) != (rows,):
+            raise ValueError(f"dropout_rows: sample_ids must be ({rows},)")
+    _lib.call("xp_dropout_rows", ptr(x), ptr(y), ctypes.c_void_p(mask.data_ptr()), use, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+              None if ids is None else ctypes.c_void_p(ids.data_ptr()), int(tag), float(p), rows, C, _lib.current_stream(x) if stream is None else stream)
+    return y, mask
 
 
 def _split_h2(w_nk, stream=None):
@@ -379,11 +481,234 @@ class XPointHeads(torch.nn.Module):
         return {'logits': o_det.view(B, Hc, Wc, -1).permute(0, 3, 1, 2), 'desc': desc.view(B, Hc, Wc, -1).permute(0, 3, 1, 2)}
 
 
-def finetune_step(net, heads, data, loss_fn, optimizer):
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the homography head (reference xpoint/models/RegNet.py)
+# ------------------------------------------------------------------------------------------------------------------------------------
+_HM = "hm_regressor."
+
+
+def _conv3x3_zp_h2(x, wsplit, Co, stream=None):
+    """conv3x3(zero_pad(x)), no bias, no activation, on the split-fp16 engine: x (B, H, W, Ci), wsplit = _split_h2 of w (Co, 9 Ci)."""
+    B, H, W, Ci = x.shape
+    y = torch.empty((B, H, W, Co), dtype=torch.float32, device=x.device)
+    _lib.call("xp_conv3x3_nhwc_h2", ptr(x), ctypes.c_void_p(wsplit.data_ptr()), ptr(y), None, None, None, B, H, W, Ci, Co, 1, 0, 0,
+              _lib.current_stream(x) if stream is None else stream)
+    return y
+
+
+class _Layer1Fn(torch.autograd.Function):
+    """RegNet.layer1 on one image's maps: enc (B, H, W, Ci), w1 (C1, 3, 3, Ci), gamma1, beta1, w2 (C2, 3, 3, C1), gamma2, beta2 ->
+    maxpool2(relu(y2)) (B, H / 2, W / 2, C2), the two BatchNorm outputs y1, y2 and the batch statistics (mean (2, C), biased variance) of both.
+    s1, s2: the split-fp16 planes of w1, w2 (made once per forward of the module: both images use them)."""
+
+    @staticmethod
+    def forward(ctx, enc, w1, g1, b1, w2, g2, b2, s1, s2):
+        B, H, W, _ = enc.shape
+        C1, C2 = w1.shape[0], w2.shape[0]
+        rows = B * H * W
+        st = _lib.current_stream(enc)
+        z1 = _conv3x3_zp_h2(enc, s1, C1, stream=st)
+        y1, m1, i1, v1 = bn_train_fwd(z1.view(rows, C1), g1.contiguous(), b1.contiguous(), stream=st)
+        r1 = _relu(y1, stream=st).view(B, H, W, C1)
+        z2 = _conv3x3_zp_h2(r1, s2, C2, stream=st)
+        y2, m2, i2, v2 = bn_train_fwd(z2.view(rows, C2), g2.contiguous(), b2.contiguous(), stream=st)
+        y2 = y2.view(B, H, W, C2)
+        pooled = torch.empty((B, H // 2, W // 2, C2), dtype=torch.float32, device=enc.device)
+        _lib.call("xp_maxpool2_nhwc", ptr(y2), ptr(pooled), B, H, W, C2, st)
+        a = _relu(pooled, stream=st)                       # relu(maxpool(y)) == maxpool(relu(y)), value for value: the ReLU is monotone
+        y1 = y1.view(B, H, W, C1)
+        ctx.save_for_backward(enc, z1, y1, r1, z2, y2, w2, g1, g2, m1, i1, m2, i2)
+        ctx.mark_non_differentiable(y1, y2, m1, v1, m2, v2)
+        return a, y1, y2, m1, v1, m2, v2
+
+    @staticmethod
+    def backward(ctx, da, *_rest):
+        enc, z1, y1, r1, z2, y2, w2, g1, g2, m1, i1, m2, i2 = ctx.saved_tensors
+        B, H, W, C1 = y1.shape
+        C2 = y2.shape[-1]
+        rows = B * H * W
+        st = _lib.current_stream(enc)
+        dy2 = maxpool2_relu_bwd(da.contiguous(), y2, stream=st)
+        dz2, dg2, db2, sc2 = bn_train_bwd(dy2.view(rows, C2), z2.view(rows, C2), g2.contiguous(), m2, i2, scaled=True, stream=st)
+        dz2 = dz2.view(B, H, W, C2)
+        dw2 = conv3x3_wgrad_zero_pad(r1, dz2, sc2, stream=st)
+        dr1 = conv3x3_dgrad(dz2, w2, sc2, stream=st)        # unscaled: 1 / S is applied in the engine's epilogue
+        dy1 = relu_bwd(dr1, y1, stream=st)
+        dz1, dg1, db1, sc1 = bn_train_bwd(dy1.view(rows, C1), z1.view(rows, C1), g1.contiguous(), m1, i1, scaled=True, stream=st)
+        dw1 = conv3x3_wgrad_zero_pad(enc, dz1.view(B, H, W, C1), sc1, stream=st)
+        return None, dw1, dg1, db1, dw2, dg2, db2, None, None
+
+
+class _CostVolumeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        B, hw, C = a.shape
+        v = torch.empty((B, hw), dtype=torch.float32, device=a.device)
+        _lib.call("xp_costvolume_mean", ptr(a), ptr(b), ptr(v), B, hw, C, _lib.current_stream(a))
+        ctx.save_for_backward(a, b)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        a, b = ctx.saved_tensors
+        return costvolume_mean_bwd(a, b, dv)
+
+
+def _transposed(x):
+    """x^T with contiguous rows of stride 1 (what `.t().contiguous()` does not promise when a dimension is 1)."""
+    out = torch.empty((x.shape[1], x.shape[0]), dtype=x.dtype, device=x.device)
+    out.copy_(x.t())
+    return out
+
+
+class _FcFn(torch.autograd.Function):
+    """RegNet.fc in training mode: v (B, K) -> Linear(relu(Linear(dropout(v))) dropped again).  masks: (m1 (B, K), m2 (B, N1)) uint8 or None (drawn from
+    seed and sample_ids with tags 0 and 1)."""
+
+    @staticmethod
+    def forward(ctx, v, w1, b1, w2, b2, p, seed, sample_ids, masks):
+        B, K = v.shape
+        N1, N2 = w1.shape[0], w2.shape[0]
+        st = _lib.current_stream(v)
+        dev = v.device
+        d1, m1 = dropout_rows(v, p, seed, sample_ids, 0, None if masks is None else masks[0], stream=st)
+        h = torch.empty((B, N1), dtype=torch.float32, device=dev)
+        _gemm_nt_h2(d1, _split_h2(w1, stream=st), N1, K, h, bias=b1.contiguous(), act=2, stream=st)
+        d2, m2 = dropout_rows(h, p, seed, sample_ids, 1, None if masks is None else masks[1], stream=st)
+        hm = torch.empty((B, N2), dtype=torch.float32, device=dev)
+        _gemm_nt_h2(d2, _split_h2(w2, stream=st), N2, N1, hm, bias=b2.contiguous(), stream=st)
+        ctx.save_for_backward(d1, h, d2, m1, m2, w1, w2)
+        ctx.p = p
+        return hm
+
+    @staticmethod
+    def backward(ctx, dhm):
+        d1, h, d2, m1, m2, w1, w2 = ctx.saved_tensors
+        st = _lib.current_stream(h)
+        dhm = dhm.contiguous()
+        dw2 = gemm_tn(dhm, d2, stream=st)
+        db2 = colsum_rows(dhm, stream=st)
+        # a linear layer's input gradient dX = dY W as the weight-gradient GEMM read the other way (reduction over the output features): its
+        # gradient operand takes one power of two per call, so any finite gradient range is accepted without a scaled copy
+        dd2 = gemm_tn(_transposed(dhm), w2.contiguous(), stream=st)
+        dh, _ = dropout_rows(dd2, ctx.p, mask=m2, stream=st)
+        dpre = relu_bwd(dh, h, stream=st)
+        dw1 = gemm_tn(dpre, d1, stream=st)
+        db1 = colsum_rows(dpre, stream=st)
+        dd1 = gemm_tn(_transposed(dpre), w1.contiguous(), stream=st)
+        dv, _ = dropout_rows(dd1, ctx.p, mask=m1, stream=st)
+        return dv, dw1, db1, dw2, db2, None, None, None, None
+
+
+class RegNetHead(torch.nn.Module):
+    """The homography regression head of XPoint (reference xpoint/models/RegNet.py) with the reference's state_dict names under `hm_regressor.`:
+
+        regnet = training.RegNetHead.from_model(net).cuda().train()
+        pred_hm = regnet(enc[:n], enc[n:], seed=step)              # (n, 8); enc: the frozen encoder's NHWC maps of both spectra
+
+    layer1 = [Conv3x3(zero pad, no bias), BatchNorm, ReLU] x 2 + MaxPool2 runs once per image — first image, then second — each call on its own
+    batch statistics, so the running statistics are updated twice per forward and num_batches_tracked advances by 2, as the reference's two
+    `self.layer1(...)` calls do.  Then F.normalize over channels, the cost volume with its global average pool, and fc = [Dropout(0.5),
+    Linear(256, 64), ReLU, Dropout(0.5), Linear(64, 8)].  Dropout masks are drawn per sample from (seed, sample id), never from the batch
+    neighbours, or given (`dropout_masks`).  In `.eval()` the forward is convmodels.regnet_forward on this module's weights.
+    Both convolutions run on the split-fp16 engine: activations must stay below 65504 in magnitude — the encoder output, and the first BatchNorm's
+    output, which batch statistics bound by |gamma| sqrt(rows) + |beta| (O(1) in this network); gradients of any finite range are accepted.
+    No gradient reaches the encoder: an input that requires grad raises NotImplementedError."""
+
+    DROPOUT_P = 0.5
+
+    def __init__(self):
+        super().__init__()
+        nn = torch.nn
+        hm = nn.Module()          # parameter containers with the reference's layout and initialisation; forward() never calls them
+        hm.layer1 = nn.Sequential(nn.Conv2d(48, 96, 3, padding=1, bias=False), nn.BatchNorm2d(96), nn.ReLU(inplace=True),
+                                  nn.Conv2d(96, 192, 3, padding=1, bias=False), nn.BatchNorm2d(192), nn.ReLU(inplace=True), nn.MaxPool2d(2))
+        hm.fc = nn.Sequential(nn.Dropout(0.5), nn.Linear(256, 64), nn.ReLU(True), nn.Dropout(0.5), nn.Linear(64, 8))
+        self.hm_regressor = hm
+        self.last_taps = None
+
+    def t(self, key):
+        """The parameter or buffer with the reference's name `key`."""
+        mod, _, leaf = key.rpartition(".")
+        return getattr(self.get_submodule(mod), leaf)
+
+    @classmethod
+    def from_model(cls, net):
+        """The homography head of a loaded models.XPoint (configuration with homography_regression_head), as a copy."""
+        sd = net.state_dict()
+        head = cls()
+        own = head.state_dict()
+        missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked")]
+        if missing:
+            raise RuntimeError(f"RegNetHead.from_model: the model holds no {missing[:3]}")
+        head.load_state_dict({k: sd[k] for k in own if k in sd}, strict=False)
+        return head
+
+    def _update_running(self, stats, rows):
+        """nn.BatchNorm2d's update of both BatchNorms' buffers from stats = [(prefix, batch mean (2, C), biased batch variance)], four launches in all."""
+        with torch.no_grad():
+            rm = [self.t(p + "running_mean") for p, _, _ in stats]
+            rv = [self.t(p + "running_var") for p, _, _ in stats]
+            torch._foreach_mul_(rm + rv, 1.0 - BN_MOMENTUM)
+            torch._foreach_add_(rm, [m[0] for _, m, _ in stats], alpha=BN_MOMENTUM)
+            torch._foreach_add_(rv, [v for _, _, v in stats], alpha=BN_MOMENTUM * rows / (rows - 1.0))       # the running value is the unbiased variance
+            torch._foreach_add_([self.t(p + "num_batches_tracked") for p, _, _ in stats], 1)
+
+    def forward(self, enc1_nhwc, enc2_nhwc, seed=0, sample_ids=None, dropout_masks=None, keep_taps=False):
+        """enc1_nhwc, enc2_nhwc (B, H', W', 48) on the GPU with (H' / 2)(W' / 2) == 256 -> (B, 8).  seed / sample_ids (int32 (B,), default 0 .. B - 1):
+        the keys of the training dropout; dropout_masks = (m1 (B, 256), m2 (B, 64)) uint8 replaces the draws; keep_taps: keep the BatchNorm outputs
+        before the two ReLUs as self.last_taps = {'y1': [image 1, image 2], 'y2': [...]} (NHWC)."""
+        for e in (enc1_nhwc, enc2_nhwc):
+            _need_device(e, "RegNetHead")
+            if e.requires_grad:
+                raise NotImplementedError("RegNetHead: the encoder is frozen in this build (no gradient is passed to it); pass detached encoder maps")
+        w1 = self.t(_HM + "layer1.0.weight")
+        if enc1_nhwc.dim() != 4 or enc1_nhwc.shape[-1] != w1.shape[1] or enc2_nhwc.shape != enc1_nhwc.shape:
+            raise ValueError(f"RegNetHead: both inputs must be (B, H', W', {w1.shape[1]}), got {tuple(enc1_nhwc.shape)} and {tuple(enc2_nhwc.shape)}")
+        if w1.device != enc1_nhwc.device or enc2_nhwc.device != enc1_nhwc.device:
+            raise _lib.XPointHipError("RegNetHead: parameters and inputs live on different devices")
+        enc1, enc2 = (e.detach().to(torch.float32).contiguous() for e in (enc1_nhwc, enc2_nhwc))
+        B, H, W, _ = enc1.shape
+        fw1, fw2 = self.t(_HM + "fc.1.weight"), self.t(_HM + "fc.4.weight")
+        with torch.cuda.device(enc1.device):
+            if not self.training:
+                from .convmodels import regnet_forward, regnet_weights
+                with torch.no_grad():          # the BatchNorm affines from host copies, as models.XPoint folds them after load_state_dict
+                    host = {k: v.detach().cpu() for k, v in self.state_dict().items()}
+                    return regnet_forward(regnet_weights(host, enc1.device), enc1, enc2)
+            rows, hw = B * H * W, (H // 2) * (W // 2)
+            if rows < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size((B, w1.shape[0], H, W))}")
+            if hw != fw1.shape[1]:
+                raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({B}x{hw} and {fw1.shape[1]}x{fw1.shape[0]})")
+            if dropout_masks is not None:
+                dropout_masks = tuple(m.to(device=enc1.device, dtype=torch.uint8).contiguous() for m in dropout_masks)
+            if sample_ids is not None:
+                sample_ids = torch.as_tensor(sample_ids, dtype=torch.int32, device=enc1.device)
+            w2 = self.t(_HM + "layer1.3.weight")
+            w1p, w2p = w1.permute(0, 2, 3, 1).contiguous(), w2.permute(0, 2, 3, 1).contiguous()      # (Co, 3, 3, Ci); autograd permutes the gradients back
+            with torch.no_grad():
+                s1, s2 = _split_h2(w1p.view(w1.shape[0], -1)), _split_h2(w2p.view(w2.shape[0], -1))
+            args = (w1p, self.t(_HM + "layer1.1.weight"), self.t(_HM + "layer1.1.bias"), w2p, self.t(_HM + "layer1.4.weight"), self.t(_HM + "layer1.4.bias"),
+                    s1, s2)
+            feats, taps = [], {'y1': [], 'y2': []}
+            for enc in (enc1, enc2):                      # two calls of layer1, each on its own batch statistics (RegNet.py:33-34)
+                a, y1, y2, m1, v1, m2, v2 = _Layer1Fn.apply(enc, *args)
+                self._update_running([(_HM + "layer1.1.", m1, v1), (_HM + "layer1.4.", m2, v2)], rows)
+                feats.append(_L2NormFn.apply(a.view(B * hw, -1)).view(B, hw, -1))
+                taps['y1'].append(y1); taps['y2'].append(y2)
+            self.last_taps = taps if keep_taps else None
+            v = _CostVolumeFn.apply(feats[0], feats[1])
+            return _FcFn.apply(v, fw1, self.t(_HM + "fc.1.bias"), fw2, self.t(_HM + "fc.4.bias"), self.DROPOUT_P, int(seed), sample_ids, dropout_masks)
+
+
+def finetune_step(net, heads, data, loss_fn, optimizer, regnet=None, seed=0):
     """One head fine-tuning step on a pair batch `data` = {'optical': {'image', 'keypoints', 'valid_mask', 'homography', ...}, 'thermal': {...}}
     (augmentation.augment_pair_batch's dict).  The frozen `net` (eval) produces the encoder output of both spectra in one forward; `heads` runs
     once per spectrum, so each spectrum has its own batch statistics and the running statistics update twice, as the reference's forward_impl
-    does per call (XPoint.py:283-323).  Returns (loss, loss_components)."""
+    does per call (XPoint.py:283-323).  regnet: a RegNetHead whose parameters the optimizer also holds: its prediction from the two spectra's encoder
+    maps (optical first, XPoint.py:210) goes to the loss as 'pred_hm' (the loss needs homography_regression_loss.check and data['hfour_points']);
+    `seed` keys its dropout for this step (pass the step number).  Returns (loss, loss_components)."""
     opt, th = data['optical'], data['thermal']
     n = opt['image'].shape[0]
     if net.training:
@@ -398,7 +723,11 @@ def finetune_step(net, heads, data, loss_fn, optimizer):
     optimizer.zero_grad(set_to_none=True)
     pred = heads(enc[:n])
     pred2 = heads(enc[n:])
-    loss, components = loss_fn({'data': data, 'pred': pred, 'pred2': pred2})
+    loss_input = {'data': data, 'pred': pred, 'pred2': pred2}
+    if regnet is not None:
+        regnet.train()
+        loss_input['pred_hm'] = regnet(enc[:n], enc[n:], seed=seed)
+    loss, components = loss_fn(loss_input)
     loss.backward()
     optimizer.step()
     return loss.detach(), components
