@@ -747,6 +747,43 @@ int xp_dropout_rows(const float* x, float* y, unsigned char* mask /* u8, in or o
                     int tag, float p, int rows, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training of a VSS encoder block (xpoint_amd/training.py VSSBlock; csrc/train_vss.hip, xp_scale_grad in csrc/train_dense.hip; DESIGN.md section 16;
+ * reference VMamba.py:1153-1234 with the SS2D of forwardv2 / forward_corev2).  The block's dense layers run on xp_gemm_nt_h2 / xp_gemm_tn_h2 /
+ * xp_colsum_rows and its SS2D core on xp_cross_scan / xp_selective_scan_fwd_x / xp_selective_scan_bwd_typed / xp_cross_merge; the entries below are
+ * the HBM-bound rest.  All tensors are contiguous f32 rows; no atomics: every cross-row sum runs in a fixed order with f64 accumulators (the
+ * reduction of xp_bn_train_bwd: 64 row groups of 8 lanes, lanes then groups in order), so two calls are bit-identical.
+ *
+ * dx_scale (xp_layernorm_bwd, xp_dwconv3x3_silu_bwd, xp_gelu_bwd): NULL, or a device float[2] that receives {S, 1 / S} with max|dx| S in
+ *   [2^13, 2^14); dx is then written as S x the gradient — xp_bn_train_bwd's contract, the operand format xp_gemm_tn_h2 (p_scale) and
+ *   xp_gemm_nt_h2 (1 / S in the epilogue's scale vector) read next.  An all-zero dx gives S = 1; non-finite elements take no part in S.
+ * xp_scale_grad: the same for a gradient that arrives from elsewhere (the block's incoming dy, the scan / cross-merge backward): out = S g over n
+ *   elements (out may be g), scale_out = {S, 1 / S}; built from the amax / power-of-two / scale kernels of xp_gemm_tn_h2.  Any finite range is
+ *   accepted.  Workspace: xp_scale_grad_workspace_bytes() = 4352 bytes.
+ * xp_layernorm_bwd: backward of xp_layernorm (gelu = 0) over (rows, C): x is the forward's INPUT; mean and rstd are recomputed per row with the
+ *   forward's lane geometry and arithmetic, so xhat = (x - mean) rstd is the forward's xhat bit for bit.  With g = gamma dy:
+ *   dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (the row sums and the bracket in f64), dgamma = sum_r dy xhat, dbeta = sum_r dy (either may be
+ *   NULL).  rows >= 1, C a multiple of 4 up to 1024, pointers 16-byte aligned.  Workspace: xp_layernorm_bwd_workspace_bytes(rows, C), 256-byte aligned.
+ * xp_dwconv3x3_silu_bwd: backward of xp_dwconv3x3_silu (zero padding 1, no bias, w9c (9, C)): z = dwconv(x) is recomputed,
+ *   dz = dy sigma(z) (1 + z (1 - sigma(z))) goes to the workspace, dx = the convolution of dz with the taps mirrored (a tap outside the image
+ *   contributes 0; nothing crosses a sample boundary, so a sample's dx does not depend on its batch neighbours), dw9c[t][c] = sum_{b,y,x} dz
+ *   x_shifted(t) (may be NULL).  C a multiple of 4, H, W >= 1.  Workspace: xp_dwconv3x3_silu_bwd_workspace_bytes(batch, H, W, C), 256-byte aligned.
+ * xp_gelu_fwd: y = GELU(x) with the function of the GEMM epilogue's act = 1 (erf form), so a dense launch with act = 0 followed by xp_gelu_fwd
+ *   equals the same launch with act = 1 bit for bit.  xp_gelu_bwd: dx = dy (Phi(x) + x phi(x)); workspace (4352 bytes) only with dx_scale.
+ * xp_add_scaled_rows: y = x + s[b] r over (batch rows_per_sample, C) rows, s (batch) f32: the residual add under stochastic depth.  x = NULL:
+ *   y = s[b] r, its backward.  y may alias x or r.  batch <= 65535. */
+size_t xp_scale_grad_workspace_bytes(void);
+int xp_scale_grad(const float* g, float* out, int64_t n, float* scale_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_layernorm_bwd_workspace_bytes(int64_t rows, int C);
+int xp_layernorm_bwd(const float* dy, const float* x, const float* gamma, float* dx, float* dgamma, float* dbeta, int64_t rows, int C, float eps,
+                     float* dx_scale, void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_dwconv3x3_silu_bwd_workspace_bytes(int batch, int H, int W, int C);
+int xp_dwconv3x3_silu_bwd(const float* x, const float* w9c, const float* dy, float* dx, float* dw9c, int batch, int H, int W, int C, float* dx_scale,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int xp_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
+int xp_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, float* dx_scale, void* workspace, size_t workspace_bytes, void* stream);
+int xp_add_scaled_rows(const float* x, const float* r, const float* s, float* y, int batch, int64_t rows_per_sample, int C, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -1,0 +1,127 @@
+"""Timing and peak memory of one VSS block's training step on the HIP library (xpoint_amd.training.VSSBlock, forward + backward with the input gradient)
+against torch eager autograd of the same block, f32, on the same GPU.
+
+    python tools/vss_train_bench.py [--iters 20] [--batch 16]
+
+Shapes: the reference's training crop (256 x 256, batch 16) at the first and the last encoder stage — (16, 64, 64, 96) and (16, 8, 8, 768).  The eager
+side is the reference's forward_corev2 written with torch here, its selective scan and cross scan / merge bound to xpoint_amd.kernels (the only way the
+reference trains on ROCm); everything else — LayerNorm, the linear layers, the depthwise convolution, the einsums, GELU — is
+torch.  Both sides hold the same weights, so the two results are compared as a sanity figure.  The two sides alternate in the same call; device events
+after a warm-up, `--iters` iterations each (the method of tools/regnet_train_bench.py), next to each the time the host needs to issue an iteration;
+then the HIP side's per-kernel split from the library's event profiler (one profiled iteration).  One JSON line per shape; nothing is asserted."""
+import argparse
+import copy
+import ctypes
+import json
+import os
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from xpoint_amd import _lib, training  # noqa: E402
+from xpoint_amd.kernels import cross_merge_fn, cross_scan_fn, selective_scan_fn  # noqa: E402
+
+
+def eager_forward(blk, x):
+    """VMamba.py:1222-1234 with forwardv2 / forward_corev2 (v05_noz, d_state 1) on the parameters of `blk`; x (B, H, W, C)"""
+    t = blk.t
+    B, H, W, C = x.shape
+    L = H * W
+    R = blk.dt_rank
+    y = F.layer_norm(x, (C,), t("norm.weight"), t("norm.bias"), 1e-5)
+    y = F.silu(F.conv2d(F.linear(y, t("op.in_proj.weight")).permute(0, 3, 1, 2).contiguous(), t("op.conv2d.weight"), padding=1, groups=C))
+    xs = cross_scan_fn(y, in_channel_first=True, out_channel_first=True, scans=0)
+    x_dbl = torch.einsum("b k d l, k c d -> b k c l", xs, t("op.x_proj_weight"))
+    dts, Bs, Cs = torch.split(x_dbl, [R, 1, 1], dim=2)
+    dts = torch.einsum("b k r l, k d r -> b k d l", dts, t("op.dt_projs_weight"))
+    ys = selective_scan_fn(xs.view(B, -1, L), dts.contiguous().view(B, -1, L), -t("op.A_logs").float().exp(), Bs.contiguous(), Cs.contiguous(),
+                           t("op.Ds").float(), t("op.dt_projs_bias").view(-1).float(), True)
+    y = cross_merge_fn(ys.view(B, 4, C, H, W), in_channel_first=True, out_channel_first=True, scans=0)
+    y = y.view(B, C, L).transpose(1, 2).contiguous().view(B, H, W, C)
+    y = F.layer_norm(y, (C,), t("op.out_norm.weight"), t("op.out_norm.bias"), 1e-5)
+    x = x + F.linear(y, t("op.out_proj.weight"))
+    y = F.layer_norm(x, (C,), t("norm2.weight"), t("norm2.bias"), 1e-5)
+    return x + F.linear(F.gelu(F.linear(y, t("mlp.fc1.weight"), t("mlp.fc1.bias"))), t("mlp.fc2.weight"), t("mlp.fc2.bias"))
+
+
+def measure(step, iters):
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        step()
+    host_ms = (time.perf_counter() - t0) * 1e3 / iters          # time the host needs to ISSUE an iteration (no synchronisation inside)
+    e1.record()
+    torch.cuda.synchronize()
+    measure.host_ms = host_ms
+    return e0.elapsed_time(e1) / iters, (torch.cuda.max_memory_allocated() - base) / 2**20
+
+
+def kernel_split(step):
+    lib = _lib.load()
+    lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
+    step(); torch.cuda.synchronize()
+    lib.xp_prof_enable(0)
+    name = ctypes.create_string_buffer(96); ms = ctypes.c_double(); cnt = ctypes.c_int(); fl = ctypes.c_double(); by = ctypes.c_double()
+    rows = {}
+    for i in range(lib.xp_prof_count()):
+        lib.xp_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by))
+        rows[name.value.decode()] = {"us": round(ms.value * 1e3, 1), "launches": cnt.value}
+    return dict(sorted(rows.items(), key=lambda kv: -kv[1]["us"]))
+
+
+def bench(shape, iters):
+    B, H, W, C = shape
+    torch.manual_seed(0)                                     # the block's initialisation: the same weights in every run
+    hip = training.VSSBlock(C).cuda().train()
+    eager = copy.deepcopy(hip)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x0 = torch.randn(shape, device="cuda", generator=g)
+    R = torch.randn(shape, device="cuda", generator=g)
+    grads = {}
+
+    def run(tag, mod, forward):
+        def step():
+            for p in mod.parameters():
+                p.grad = None
+            x = x0.clone().requires_grad_(True)
+            (forward(x) * R).sum().backward()
+            grads[tag] = x.grad
+        return step
+    step_hip = run("hip", hip, hip)
+    step_eager = run("eager", eager, lambda x: eager_forward(eager, x))
+    res = {"shape": list(shape), "rows": B * H * W, "iters": iters, "route_tensor_MiB": round(B * 4 * C * H * W * 4 / 2**20, 1)}
+    for rep in range(2):                                     # alternate: hip, eager, hip, eager
+        for tag, st in (("hip", step_hip), ("eager", step_eager)):
+            ms, mib = measure(st, iters)
+            res.setdefault(f"{tag}_fwd_bwd_ms", []).append(round(ms, 4))
+            res[f"{tag}_peak_MiB"] = round(mib, 1)
+            res[f"{tag}_host_issue_ms"] = round(measure.host_ms, 4)
+    res["ratio_hip_over_eager"] = round(min(res["hip_fwd_bwd_ms"]) / min(res["eager_fwd_bwd_ms"]), 3)
+    # a sanity figure, not a parity check (tests/test_gpu_vss_training.py is): eager f32 is the other side
+    pairs = list(zip(hip.parameters(), eager.parameters())) + [(type("G", (), {"grad": grads["hip"]}), type("G", (), {"grad": grads["eager"]}))]
+    res["max_grad_diff_vs_eager_over_scale"] = max(float((a.grad - b.grad).abs().max() / b.grad.abs().max().clamp(min=1e-30)) for a, b in pairs)
+    res["hip_kernel_split"] = kernel_split(step_hip)
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=16)
+    args = ap.parse_args()
+    for H, C in ((64, 96), (8, 768)):
+        bench((args.batch, H, H, C), args.iters)
+
+
+if __name__ == "__main__":
+    main()

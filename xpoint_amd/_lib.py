@@ -138,6 +138,12 @@ _SIGNATURES = {
     "xp_maxpool2_relu_bwd": [c_p] * 3 + [c_i] * 4 + [c_p],
     "xp_costvolume_mean_bwd": [c_p] * 5 + [c_i] * 3 + [c_p],
     "xp_dropout_rows": [c_p, c_p, c_p, c_i, ctypes.c_uint64, c_p, c_i, c_f, c_i, c_i, c_p],
+    "xp_scale_grad": [c_p, c_p, c_l, c_p, c_p, c_sz, c_p],
+    "xp_layernorm_bwd": [c_p] * 6 + [c_l, c_i, c_f, c_p, c_p, c_sz, c_p],
+    "xp_dwconv3x3_silu_bwd": [c_p] * 5 + [c_i] * 4 + [c_p, c_p, c_sz, c_p],
+    "xp_gelu_fwd": [c_p, c_p, c_l, c_p],
+    "xp_gelu_bwd": [c_p, c_p, c_p, c_l, c_p, c_p, c_sz, c_p],
+    "xp_add_scaled_rows": [c_p] * 4 + [c_i, c_l, c_i, c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -181,6 +187,9 @@ _SIZE_QUERIES = {
     "xp_gemm_tn_h2_workspace_bytes": (c_sz, [c_i] * 3),
     "xp_bn_workspace_bytes": (c_sz, [c_i]),
     "xp_conv3x3_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
+    "xp_scale_grad_workspace_bytes": (c_sz, []),
+    "xp_layernorm_bwd_workspace_bytes": (c_sz, [c_l, c_i]),
+    "xp_dwconv3x3_silu_bwd_workspace_bytes": (c_sz, [c_i] * 4),
 }
 
 

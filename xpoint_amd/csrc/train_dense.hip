@@ -1,6 +1,8 @@
 // Dense backward kernels of head training: the weight-gradient GEMM on the split-fp16 matrix path, its implicit 3x3 form,
 // BatchNorm training forward / backward over NHWC rows, the column sums behind the bias gradients and the L2-normalise backward; at the end of the
-// file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head.
+// file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head, and xp_scale_grad, the amax / power-of-two
+// / scale kernels of the weight gradient as an entry point of their own (VSS-block training).  The row walks and the fixed-order column sums
+// are in train_rows.h, which train_vss.hip shares.
 //
 // Weight gradient.  out[i][j] = sum_m P[m][i] Q[m][j]: the reduction runs over the SLOW dimension of both operands, so a 32-row slab of each is split
 // into its two fp16 planes (gemm_h2_core.h) in registers and stored to the LDS in the transposed image — tile row = output row / column, 32 k values
@@ -11,6 +13,7 @@
 // M is cut into chunks of WG_CHUNK rows — a compile-time constant — one workgroup per (tile, chunk); the partial tiles go to the workspace and a second
 // kernel adds them in chunk order: no atomics, two calls are bit-identical, and a result does not depend on the device.
 #include "gemm_h2_core.h"
+#include "train_rows.h"
 #include "xpoint_hip.h"
 
 #ifndef XP_TRY
@@ -27,14 +30,6 @@ constexpr int WG_HEAD_BYTES = AMAX_PARTS * 4 + 256;   // workspace head: partial
 static_assert(WG_CHUNK == XP_WGRAD_CHUNK, "the header quotes the chunk length");
 
 // ---- largest magnitude of a (rows x C, ld) matrix and its power of two: maxima are order-free, hence deterministic ----
-// element-wise walks: a block is 4 rows x 64 channel lanes (one wave per row, 256-byte segments), rows strided by the grid: no division per element
-template <class F>
-__device__ __forceinline__ void td_for_each(int64_t rows, int C, F f) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
-        for (int c = lane; c < C; c += 64) f(r, c);
-}
-
 __global__ __launch_bounds__(256) void td_amax_kernel(const float* __restrict__ x, int64_t rows, int C, int ld, float* __restrict__ part) {
     float m = 0.f;
     td_for_each(rows, C, [&](int64_t r, int c) { m = fmaxf(m, fabsf(x[r * ld + c])); });
@@ -231,40 +226,6 @@ static int td_wgrad_launch(const char* who, int conv, WgParams p, float* out, in
     hipLaunchKernelGGL(td_wgrad_sum_kernel, dim3(xp_cdiv((int64_t)p.I * p.J, 256)), dim3(256), 0, s, p.part, p.scale, nchunk, p.I, p.J, ldo, out);
     XP_LAUNCH_CHECK();
     return XP_OK;
-}
-
-// ---- per-channel sums over (rows x C) in a fixed order ----
-// A block is 32 channels x 8 row lanes; BN_PARTS blocks share the rows of a channel group (row r belongs to part (r / 8) % BN_PARTS, lane r % 8).  Every
-// thread accumulates in f64 (as det_reduce_kernel does), the 8 lanes are added in lane order, and the finishing kernels add the parts in part order.
-constexpr int BN_PARTS = 64;
-
-template <int NQ, class F>
-__device__ __forceinline__ void td_colsum_parts(int64_t rows, int C, double* __restrict__ part, F f) {
-    __shared__ double sm[NQ][8][32];
-    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5, c = blockIdx.x * 32 + cl, pt = blockIdx.y;
-    double a[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) a[q] = 0.0;
-    if (c < C) {
-#pragma unroll 4
-        for (int64_t r = (int64_t)pt * 8 + rl; r < rows; r += BN_PARTS * 8) f(r, c, a);
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) sm[q][rl][cl] = a[q];
-    __syncthreads();
-    if (rl == 0 && c < C) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            double s = sm[q][0][cl];
-            for (int k = 1; k < 8; ++k) s += sm[q][k][cl];
-            part[((size_t)pt * NQ + q) * C + c] = s;
-        }
-    }
-}
-__device__ __forceinline__ double td_sum_parts(const double* __restrict__ part, int NQ, int q, int C, int c) {
-    double s = part[(size_t)q * C + c];
-    for (int k = 1; k < BN_PARTS; ++k) s += part[((size_t)k * NQ + q) * C + c];
-    return s;
 }
 
 // BatchNorm forward statistics on data shifted by the channel's first element (exact in f64): sum d, sum d^2.  The saved mean is (2, C): the f32 mean
@@ -562,4 +523,32 @@ extern "C" int xp_conv3x3_dgrad_h2(const float* dy, const float* w, float* dx, i
     XP_TRY(xp_split_weights_h2(wrot, ws + l.wsplit, Ci, 9 * Co, stream));
     // dx = conv3x3(zero_pad(S dy), wrot) / S on the forward's implicit-GEMM engine: no atomics, the engine's fixed summation order
     return xp_conv3x3_nhwc_h2(dy, ws + l.wsplit, dx, nullptr, vscale, vshift, batch, H, W, Co, Ci, 1, 0, 0, stream);
+}
+
+// ---- one power of two for a gradient that arrives from elsewhere (the block's incoming dy, the scan / cross-scan backward): DESIGN.md §16 ----
+extern "C" size_t xp_scale_grad_workspace_bytes(void) { return WG_HEAD_BYTES; }
+
+extern "C" int xp_scale_grad(const float* g, float* out, int64_t n, float* scale_out, void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(g && out && scale_out && n > 0 && n < ((int64_t)1 << 40), "xp_scale_grad: null pointer or bad n = %lld", (long long)n);
+    XP_CHECK_ARG(workspace && workspace_bytes >= (size_t)WG_HEAD_BYTES, "xp_scale_grad: workspace of %d bytes needed", WG_HEAD_BYTES);
+    hipStream_t s = (hipStream_t)stream;
+    float* amax = (float*)workspace;
+    float2* scale = (float2*)scale_out;
+    // the flat vector as (n / 256) rows of 256 and one tail row: the walks of the weight gradient's amax / scale kernels, no second copy
+    const int64_t rows = n / 256;
+    const int tail = (int)(n - rows * 256);
+    const int nb = rows ? (int)min((int64_t)AMAX_PARTS - 1, (rows + 3) / 4) : 0;
+    XpProfScope prof("scale_grad", s, 0.0, 12.0 * n);
+    if (rows) { hipLaunchKernelGGL(td_amax_kernel, dim3(nb), dim3(256), 0, s, g, rows, 256, 256, amax); XP_LAUNCH_CHECK(); }
+    if (tail) { hipLaunchKernelGGL(td_amax_kernel, dim3(1), dim3(256), 0, s, g + rows * 256, (int64_t)1, tail, tail, amax + nb); XP_LAUNCH_CHECK(); }
+    hipLaunchKernelGGL(td_scale_kernel, dim3(1), dim3(256), 0, s, amax, nb + (tail ? 1 : 0), scale);
+    XP_LAUNCH_CHECK();
+    if (out == g) {
+        if (rows) { hipLaunchKernelGGL(td_mul_scale_kernel, dim3(nb), dim3(256), 0, s, out, rows, 256, 256, scale); XP_LAUNCH_CHECK(); }
+        if (tail) { hipLaunchKernelGGL(td_mul_scale_kernel, dim3(1), dim3(256), 0, s, out + rows * 256, (int64_t)1, tail, tail, scale); XP_LAUNCH_CHECK(); }
+    } else {
+        if (rows) { hipLaunchKernelGGL(td_scaled_copy_kernel, dim3(nb), dim3(256), 0, s, g, out, rows, 256, scale); XP_LAUNCH_CHECK(); }
+        if (tail) { hipLaunchKernelGGL(td_scaled_copy_kernel, dim3(1), dim3(256), 0, s, g + rows * 256, out + rows * 256, (int64_t)1, tail, scale); XP_LAUNCH_CHECK(); }
+    }
+    return XP_OK;
 }
