@@ -66,7 +66,10 @@ def test_training_module_host_side():
         heads(torch.zeros(1, 2, 2, 48))
     with pytest.raises(_lib.XPointHipError, match="no CPU fallback"):
         training.gemm_tn(torch.zeros(4, 3), torch.zeros(4, 5))
-    assert "oracle" not in open(training.__file__).read().replace("no import of oracle", "")
+    sources = sorted(f for f in os.listdir(os.path.dirname(training.__file__)) if f.endswith(".py"))
+    assert {"__init__.py", "ops.py", "heads.py", "regnet.py", "vss.py"} <= set(sources)
+    for f in sources:          # every file of the package
+        assert "oracle" not in open(os.path.join(os.path.dirname(training.__file__), f)).read().replace("no import of oracle", ""), f
 
 
 def test_new_exports_are_bound():

@@ -125,10 +125,10 @@ def test_drop_path_rate_table():
     with pytest.raises(ValueError):
         training.VSSBlock(32, drop_path=1.0)
     # host draws: keyed by (seed, sample id, branch), never by the position in the batch
-    a = training._drop_path_draws(0.5, 7, [0, 1, 2, 3, 4, 5, 6, 7], 0)
-    b = training._drop_path_draws(0.5, 7, [7, 6, 5, 4, 3, 2, 1, 0], 0)
+    a = training.vss._drop_path_draws(0.5, 7, [0, 1, 2, 3, 4, 5, 6, 7], 0)
+    b = training.vss._drop_path_draws(0.5, 7, [7, 6, 5, 4, 3, 2, 1, 0], 0)
     assert a == b[::-1] and set(a) == {0.0, 2.0}
-    assert a != training._drop_path_draws(0.5, 7, range(8), 1) or a != training._drop_path_draws(0.5, 8, range(8), 0)
+    assert a != training.vss._drop_path_draws(0.5, 7, range(8), 1) or a != training.vss._drop_path_draws(0.5, 8, range(8), 0)
 
 
 def test_new_exports_are_bound():

@@ -7,29 +7,10 @@ import pytest
 import torch
 
 from tests import heads_f64 as Hd
+from tests.training_cases import AUG_CFG, LOSS_CFG, _bits, _close, _im2col, _net, _rand
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
 CHUNK = 256           # XP_WGRAD_CHUNK of include/xpoint_hip.h (pinned by test_chunk_constant)
-
-
-def _close(got, ref, what, tol=TOL, scale=None):
-    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
-    ref = torch.as_tensor(np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref)).double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), what
-    err, sc = float((got - ref).abs().max()), float(ref.abs().max()) if scale is None else scale
-    print(f"{what}: err / scale = {err / max(sc, 1e-300):.2e} (scale {sc:.3e})")
-    assert err <= tol * max(sc, 1e-30), (what, err, sc)
-
-
-def _rand(shape, seed, lo=-1.0, hi=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g, dtype=torch.float64) * (hi - lo) + lo).float()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 def test_chunk_constant():
@@ -77,12 +58,6 @@ def test_gemm_tn_column_slices(gpu_lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------- convolution weight gradient
-def _im2col(x_nhwc):
-    B, H, W, Ci = x_nhwc.shape
-    xp = torch.nn.functional.pad(x_nhwc.permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect")
-    return torch.cat([xp[:, :, ky:ky + H, kx:kx + W].permute(0, 2, 3, 1).reshape(B * H * W, Ci) for ky in range(3) for kx in range(3)], 1).contiguous()
-
-
 @pytest.mark.parametrize("shape", [(1, 2, 2, 4, 8), (1, 3, 5, 48, 32), (3, 9, 7, 48, 512), (2, 33, 32, 48, 64)])
 def test_conv3x3_wgrad(gpu_lib, shape):
     """(1, 2, 2, 4, 8): both reflected indices fold onto the same image; (2, 33, 32, ..): 1056 rows per image, no multiple of the chunk length: chunk boundaries fall
@@ -278,15 +253,6 @@ def test_heads_training_step_is_repeatable(gpu_lib):
     assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 
-def _net(kind):
-    from xpoint_amd import models, synth
-    cfg = Hd.model_config(kind)
-    net = models.XPoint(cfg)
-    net.load_state_dict(synth.make_torch_state_dict(cfg) if kind == "vmamba" else
-                        {k: torch.from_numpy(np.array(v, copy=True)) for k, v in synth.make_conv_xpoint_state_dict(cfg).items()}, strict=True)
-    return net.to("cuda").eval()
-
-
 @pytest.mark.parametrize("kind", Hd.CONFIGS)
 def test_eval_heads_equal_the_inference_path(gpu_lib, kind):
     from xpoint_amd import training as T
@@ -316,16 +282,6 @@ def test_heads_refusals(gpu_lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------- one fine-tuning run
-LOSS_CFG = {'detector_loss': True, 'detector_use_cross_entropy': True, 'descriptor_loss': True, 'descriptor_loss_threshold': 4.0,
-            'descriptor_loss_use_mask': True, 'sparse_descriptor_loss': False, 'sparse_descriptor_loss_num_cell_divisor': 64,
-            'positive_margin': 1.0, 'negative_margin': 0.2, 'lambda_d': 250, 'lambda': 1.0, 'use_encoder_similarity': False,
-            'homography_regression_loss': {'check': False, 'gamma': 1.0}, 'detector_loss_function': 'cross_entropy',
-            'detector_handle_multiple_keypoints': 'hard_assignment', 'detector_dustbin_loss_weight': 1,
-            'detector_focal_loss': {'use': False, 'alpha': 0.25, 'gamma': 2.0, 'reduction': 'mean'}}
-AUG_CFG = {'photometric': {'enable': True, 'primitives': ['random_brightness', 'random_contrast', 'additive_gaussian_noise'], 'random_order': False,
-                           'params': {'random_brightness': {'max_abs_change': 0.15}, 'random_contrast': {'strength_range': [0.3, 1.8]},
-                                      'additive_gaussian_noise': {'stddev_range': [0, 0.06]}}},
-           'homographic': {'enable': False}}         # the homographic branch needs room for a 128 x 128 crop; this pair is 64 x 96
 STEPS, LR = 8, 1e-3
 
 

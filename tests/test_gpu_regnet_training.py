@@ -12,40 +12,15 @@ import torch
 import torch.nn.functional as F
 
 from tests import regnet_f64 as Rg
+from tests.training_cases import AUG_CFG_HM as AUG_CFG, LOSS_CFG_HM as LOSS_CFG, _bits, _close, _im2col_zero, _net, _rand
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
 CHUNK = 256           # XP_WGRAD_CHUNK of include/xpoint_hip.h
 GATE_MARGIN = 1e-5    # of the layer's scale: how close to the jump a decision must be for the two sides to be allowed to differ
 GATE_SHARE = 1e-4     # of all decisions
 
 
-def _close(got, ref, what, tol=TOL, scale=None):
-    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
-    ref = torch.as_tensor(np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref)).double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), what
-    err, sc = float((got - ref).abs().max()), float(ref.abs().max()) if scale is None else scale
-    print(f"{what}: err / scale = {err / max(sc, 1e-300):.2e} (scale {sc:.3e})")
-    assert err <= tol * max(sc, 1e-30), (what, err, sc)
-
-
-def _rand(shape, seed, lo=-1.0, hi=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g, dtype=torch.float64) * (hi - lo) + lo).float()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
 # ---------------------------------------------------------------------------------------------------------------- zero-pad convolution gradients
-def _im2col_zero(x_nhwc):
-    B, H, W, Ci = x_nhwc.shape
-    xp = F.pad(x_nhwc.permute(0, 3, 1, 2), (1, 1, 1, 1))
-    return torch.cat([xp[:, :, ky:ky + H, kx:kx + W].permute(0, 2, 3, 1).reshape(B * H * W, Ci) for ky in range(3) for kx in range(3)], 1).contiguous()
-
-
 CONV_SHAPES = [(1, 1, 1, 4, 8), (3, 9, 7, 12, 20), (1, 257, 1, 8, 4), (2, 16, 16, 96, 192)]
 
 
@@ -277,14 +252,6 @@ def test_regnet_seeded_dropout(gpu_lib):
     assert hm1.requires_grad and hm1.shape == (3, 8)
 
 
-def _net():
-    from xpoint_amd import models, synth
-    cfg = Rg.model_config()
-    net = models.XPoint(cfg)
-    net.load_state_dict(synth.make_torch_state_dict(cfg), strict=True)
-    return net.to("cuda").eval()
-
-
 def test_eval_head_is_the_inference_path(gpu_lib):
     from xpoint_amd import convmodels, training as T
     enc1, enc2, R = Rg.case_inputs("2x64x16")
@@ -333,20 +300,6 @@ def test_regnet_refusals(gpu_lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------- one fine-tuning run
-LOSS_CFG = {'detector_loss': True, 'detector_use_cross_entropy': True, 'descriptor_loss': True, 'descriptor_loss_threshold': 4.0,
-            'descriptor_loss_use_mask': True, 'sparse_descriptor_loss': False, 'sparse_descriptor_loss_num_cell_divisor': 64,
-            'positive_margin': 1.0, 'negative_margin': 0.2, 'lambda_d': 250, 'lambda': 1.0, 'use_encoder_similarity': False,
-            'homography_regression_loss': {'check': True, 'gamma': 1.0}, 'detector_loss_function': 'cross_entropy',
-            'detector_handle_multiple_keypoints': 'hard_assignment', 'detector_dustbin_loss_weight': 1,
-            'detector_focal_loss': {'use': False, 'alpha': 0.25, 'gamma': 2.0, 'reduction': 'mean'}}
-AUG_CFG = {'photometric': {'enable': True, 'primitives': ['random_brightness', 'random_contrast', 'additive_gaussian_noise'], 'random_order': False,
-                           'params': {'random_brightness': {'max_abs_change': 0.15}, 'random_contrast': {'strength_range': [0.3, 1.8]},
-                                      'additive_gaussian_noise': {'stddev_range': [0, 0.06]}}},
-           'homographic': {'enable': True, 'valid_border_margin': 0, 'border_reflect': True,
-                           'params': {'corner_homography': {'enable': False, 'params': {'patch_size': 128, 'rho': 32}}, 'translation': True,
-                                      'rotation': True, 'scaling': True, 'perspective': True, 'scaling_amplitude': 0.2,
-                                      'perspective_amplitude_x': 0.2, 'perspective_amplitude_y': 0.2, 'patch_ratio': 0.85, 'max_angle': 1.57,
-                                      'allow_artifacts': True, 'translation_overflow': 0.05}}}
 STEPS, LR = 3, 1e-3
 
 

@@ -11,29 +11,15 @@ import torch
 import torch.nn.functional as F
 
 from tests import vss_f64 as V
+from tests.training_cases import TOL, _bits, _close
 from xpoint_amd import synth
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
 KEYS = ["out", "grad/x"] + ["grad/" + k for k in V.LEAVES]
-
-
-def _close(got, ref, what, tol=TOL, scale=None):
-    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
-    ref = torch.as_tensor(np.asarray(ref.detach().cpu() if torch.is_tensor(ref) else ref)).double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), what
-    err, sc = float((got - ref).abs().max()), float(ref.abs().max()) if scale is None else scale
-    print(f"{what}: err / scale = {err / max(sc, 1e-300):.2e} (scale {sc:.3e})")
-    assert err <= tol * max(sc, 1e-30), (what, err, sc)
 
 
 def _u(name, shape, lo=-1.0, hi=1.0):
     return torch.from_numpy(synth.uniform("vss_gpu/" + name, shape, lo, hi))
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 def _scale_ok(scale, scaled, what):
@@ -97,9 +83,10 @@ def test_dwconv3x3_silu_bwd(gpu_lib, shape):
 def test_gelu_fwd_is_the_dense_epilogue(gpu_lib):
     """fc1 (act 0) -> xp_gelu_fwd equals fc1 (act 1) of the inference path bit for bit; 35 rows: partial tiles"""
     from xpoint_amd import _lib, training as T
+    from xpoint_amd.training import ops
     a, w, b = _u("gelu/a", (35, 32), -2.0, 2.0).cuda(), _u("gelu/w", (128, 32), -0.5, 0.5).cuda(), _u("gelu/b", (128,)).cuda()
     st = _lib.current_stream(a)
-    pre, fused = T._linear(a, w, st, bias=b), T._linear(a, w, st, bias=b, act=1)
+    pre, fused = ops._linear(a, w, st, bias=b), ops._linear(a, w, st, bias=b, act=1)
     got = T.gelu_fwd(pre)
     assert float(pre.min()) < -2.0 and float(pre.max()) > 2.0
     assert torch.equal(_bits(got), _bits(fused))
@@ -208,7 +195,8 @@ _DIR_ORDER = [0, 2, 1, 3]          # the fused core's route order (xpoint_amd/mo
 def test_eval_forward_equals_the_inference_path(gpu_lib, case):
     """VSSBlock.eval() under no_grad against the unfused launch sequence of xp_xpoint_forward (csrc/model.cpp: xp_layernorm, xp_gemm_nt_h2,
     xp_dwconv3x3_silu, xp_gemm_nt_h2, xp_ss2d_core_fwd, xp_gemm_nt_h2 + residual, xp_layernorm, fc1 with GELU, fc2 + residual) on the same weights"""
-    from xpoint_amd import _lib as L, training as T
+    from xpoint_amd import _lib as L
+    from xpoint_amd.training import ops as T
     (B, H, W, C), R, _, _ = V.CASES[case]
     p = {k: v.cuda() for k, v in V.block_state(case, torch.float32).items()}
     x = V.case_inputs(case)[0].cuda()
@@ -274,7 +262,7 @@ def test_gradient_range(gpu_lib):
 
 
 def test_stochastic_depth(gpu_lib):
-    from xpoint_amd import training as T
+    from xpoint_amd.training import vss
     x, Rw = V.case_inputs("A")
     s1, s2 = torch.tensor([0.0, 1.25]), torch.tensor([1.25, 0.0])
     blk = _block("A", drop_path=0.2)
@@ -299,7 +287,7 @@ def test_stochastic_depth(gpu_lib):
     assert torch.equal(_bits(a), _bits(b)), "seeded draws are not repeatable"
     assert torch.equal(_bits(c), _bits(a[perm.cuda()])), "a sample's draw depends on its position in the batch"
     assert not torch.equal(a, other) and not torch.equal(a, plain), "the draws do not depend on the seed / eval mode scales"
-    want = [T._drop_path_draws(0.5, 11, range(B), br) for br in (0, 1)]
+    want = [vss._drop_path_draws(0.5, 11, range(B), br) for br in (0, 1)]
     assert {0.0, 2.0} == set(want[0] + want[1])
     with torch.no_grad():
         given = hi.train()(xb.cuda(), drop_path_scale=(torch.tensor(want[0]), torch.tensor(want[1])))

@@ -3,24 +3,21 @@ eager autograd of the same heads written with torch.nn here, f32, on the same GP
 
     python tools/head_train_bench.py [--iters 20] [--batch 16] [--size 256] [--no-step]
 
-Shape: the training crop of the reference's configs/cmt.yaml — 256x256, batch 16: 16 384 rows of Ci = 48 per spectrum.  The two sides alternate
-in the same call; device events after a warm-up, `--iters` iterations each (the method of tools/loss_bench.py), and next to each the time the
-host needs to issue an iteration.  Then the HIP side's per-kernel
-split from the library's event profiler (one profiled iteration), and one `finetune_step` at that shape (synthetic weights, Adam) as a time per step
+Shape: the training crop of the reference's configs/cmt.yaml — 256x256, batch 16: 16 384 rows of Ci = 48 per spectrum.  The method is
+tools/train_bench_common.py's; then one `finetune_step` at that shape (synthetic weights, Adam) as a time per step
 with the frozen encoder's share.  One JSON line."""
 import argparse
-import ctypes
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from xpoint_amd import _lib, losses, models, synth, training  # noqa: E402
+from xpoint_amd import losses, models, synth, training  # noqa: E402
+from train_bench_common import alternate, kernel_split, measure  # noqa: E402
 
 
 class EagerHeads(torch.nn.Module):
@@ -35,37 +32,6 @@ class EagerHeads(torch.nn.Module):
     def forward(self, x_nchw):
         return {'logits': self.detector_head_convolutions(x_nchw),
                 'desc': torch.nn.functional.normalize(self.descriptor_head_convolutions(x_nchw), p=2, dim=1)}
-
-
-def measure(step, iters):
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        step()
-    host_ms = (time.perf_counter() - t0) * 1e3 / iters          # time the host needs to ISSUE an iteration (no synchronisation inside)
-    e1.record()
-    torch.cuda.synchronize()
-    measure.host_ms = host_ms
-    return e0.elapsed_time(e1) / iters, (torch.cuda.max_memory_allocated() - base) / 2**20
-
-
-def kernel_split(step):
-    lib = _lib.load()
-    lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
-    step(); torch.cuda.synchronize()
-    lib.xp_prof_enable(0)
-    name = ctypes.create_string_buffer(96); ms = ctypes.c_double(); cnt = ctypes.c_int(); fl = ctypes.c_double(); by = ctypes.c_double()
-    rows = {}
-    for i in range(lib.xp_prof_count()):
-        lib.xp_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by))
-        rows[name.value.decode()] = {"us": round(ms.value * 1e3, 1), "launches": cnt.value}
-    return dict(sorted(rows.items(), key=lambda kv: -kv[1]["us"]))
 
 
 def main():
@@ -95,13 +61,7 @@ def main():
         return step
     step_hip, step_eager = run(hip, enc), run(eager, enc_nchw)
     res = {"shape": f"{args.size}x{args.size} batch {B}", "rows": B * Hc * Hc, "iters": args.iters}
-    for rep in range(2):                                     # alternate: hip, eager, hip, eager
-        for tag, st in (("hip", step_hip), ("eager", step_eager)):
-            ms, mib = measure(st, args.iters)
-            res.setdefault(f"{tag}_fwd_bwd_ms", []).append(round(ms, 4))
-            res[f"{tag}_peak_MiB"] = round(mib, 1)
-            res[f"{tag}_host_issue_ms"] = round(measure.host_ms, 4)
-    res["ratio_hip_over_eager"] = round(min(res["hip_fwd_bwd_ms"]) / min(res["eager_fwd_bwd_ms"]), 3)
+    alternate(res, step_hip, step_eager, args.iters)
     # a sanity figure, not a parity check (tests/test_gpu_head_training.py is): eager f32 is the other side, and with 8.4 million trunk outputs a
     # pre-activation within rounding of 0 is likely — where the two sides disagree on its sign a bias gradient moves by one term of its sum (~1e-2 of
     # its scale at 16 384 rows).  3.bias / 4.bias gradients are zero in exact arithmetic (the BatchNorm behind the 1x1 layer removes a per-channel constant): left out of this figure

@@ -4,22 +4,20 @@ torch eager autograd of the same head written with torch.nn here, f32, on the sa
     python tools/regnet_train_bench.py [--iters 20] [--batch 16]
 
 Shape: the only map size the head accepts — 32 x 32 x 48 per spectrum (a 256 x 256 crop), batch 16.  Both sides apply the SAME dropout masks (the eager
-side multiplies by them), so the two results can be compared as a sanity figure.  The two sides alternate in the same call; device events after a
-warm-up, `--iters` iterations each (the method of tools/head_train_bench.py), next to each the time the host needs to issue an iteration; then the
-HIP side's per-kernel split from the library's event profiler (one profiled iteration).  One JSON line; nothing is asserted."""
+side multiplies by them), so the two results can be compared as a sanity figure.  The method is tools/train_bench_common.py's.  One JSON line; nothing is
+asserted."""
 import argparse
-import ctypes
 import json
 import os
 import sys
-import time
 
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from xpoint_amd import _lib, training  # noqa: E402
+from xpoint_amd import training  # noqa: E402
+from train_bench_common import alternate, kernel_split  # noqa: E402
 
 
 class EagerRegNet(torch.nn.Module):
@@ -40,37 +38,6 @@ class EagerRegNet(torch.nn.Module):
         v = torch.bmm(a.transpose(1, 2), b).mean(-1)           # the cost volume and its global average pool, as RegNet.forward forms them
         h = F.relu(hm.fc[1](v * m1 * 2.0))
         return hm.fc[4](h * m2 * 2.0)
-
-
-def measure(step, iters):
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        step()
-    host_ms = (time.perf_counter() - t0) * 1e3 / iters          # time the host needs to ISSUE an iteration (no synchronisation inside)
-    e1.record()
-    torch.cuda.synchronize()
-    measure.host_ms = host_ms
-    return e0.elapsed_time(e1) / iters, (torch.cuda.max_memory_allocated() - base) / 2**20
-
-
-def kernel_split(step):
-    lib = _lib.load()
-    lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
-    step(); torch.cuda.synchronize()
-    lib.xp_prof_enable(0)
-    name = ctypes.create_string_buffer(96); ms = ctypes.c_double(); cnt = ctypes.c_int(); fl = ctypes.c_double(); by = ctypes.c_double()
-    rows = {}
-    for i in range(lib.xp_prof_count()):
-        lib.xp_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by))
-        rows[name.value.decode()] = {"us": round(ms.value * 1e3, 1), "launches": cnt.value}
-    return dict(sorted(rows.items(), key=lambda kv: -kv[1]["us"]))
 
 
 def main():
@@ -100,13 +67,7 @@ def main():
     step_hip = run(hip, lambda: hip(enc1, enc2, dropout_masks=(m1, m2)))
     step_eager = run(eager, lambda: eager(x1, x2, f1, f2))
     res = {"shape": f"32x32x48 maps, batch {B}", "rows_per_image": B * Hc * Hc, "iters": args.iters}
-    for rep in range(2):                                     # alternate: hip, eager, hip, eager
-        for tag, st in (("hip", step_hip), ("eager", step_eager)):
-            ms, mib = measure(st, args.iters)
-            res.setdefault(f"{tag}_fwd_bwd_ms", []).append(round(ms, 4))
-            res[f"{tag}_peak_MiB"] = round(mib, 1)
-            res[f"{tag}_host_issue_ms"] = round(measure.host_ms, 4)
-    res["ratio_hip_over_eager"] = round(min(res["hip_fwd_bwd_ms"]) / min(res["eager_fwd_bwd_ms"]), 3)
+    alternate(res, step_hip, step_eager, args.iters)
     # a sanity figure, not a parity check (tests/test_gpu_regnet_training.py is): eager f32 is the other side, and among 5 million ReLU / max-pool
     # decisions some fall within rounding of the jump and go different ways on the two sides
     res["max_grad_diff_vs_eager_over_scale"] = max(float((a.grad - b.grad).abs().max() / b.grad.abs().max().clamp(min=1e-30))

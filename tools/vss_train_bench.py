@@ -6,23 +6,21 @@ against torch eager autograd of the same block, f32, on the same GPU.
 Shapes: the reference's training crop (256 x 256, batch 16) at the first and the last encoder stage — (16, 64, 64, 96) and (16, 8, 8, 768).  The eager
 side is the reference's forward_corev2 written with torch here, its selective scan and cross scan / merge bound to xpoint_amd.kernels (the only way the
 reference trains on ROCm); everything else — LayerNorm, the linear layers, the depthwise convolution, the einsums, GELU — is
-torch.  Both sides hold the same weights, so the two results are compared as a sanity figure.  The two sides alternate in the same call; device events
-after a warm-up, `--iters` iterations each (the method of tools/regnet_train_bench.py), next to each the time the host needs to issue an iteration;
-then the HIP side's per-kernel split from the library's event profiler (one profiled iteration).  One JSON line per shape; nothing is asserted."""
+torch.  Both sides hold the same weights, so the two results are compared as a sanity figure.  The method is
+tools/train_bench_common.py's.  One JSON line per shape; nothing is asserted."""
 import argparse
 import copy
-import ctypes
 import json
 import os
 import sys
-import time
 
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from xpoint_amd import _lib, training  # noqa: E402
+from xpoint_amd import training  # noqa: E402
+from train_bench_common import alternate, kernel_split  # noqa: E402
 from xpoint_amd.kernels import cross_merge_fn, cross_scan_fn, selective_scan_fn  # noqa: E402
 
 
@@ -48,37 +46,6 @@ def eager_forward(blk, x):
     return x + F.linear(F.gelu(F.linear(y, t("mlp.fc1.weight"), t("mlp.fc1.bias"))), t("mlp.fc2.weight"), t("mlp.fc2.bias"))
 
 
-def measure(step, iters):
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        step()
-    host_ms = (time.perf_counter() - t0) * 1e3 / iters          # time the host needs to ISSUE an iteration (no synchronisation inside)
-    e1.record()
-    torch.cuda.synchronize()
-    measure.host_ms = host_ms
-    return e0.elapsed_time(e1) / iters, (torch.cuda.max_memory_allocated() - base) / 2**20
-
-
-def kernel_split(step):
-    lib = _lib.load()
-    lib.xp_prof_reset(); lib.xp_prof_filter(None); lib.xp_prof_enable(1)
-    step(); torch.cuda.synchronize()
-    lib.xp_prof_enable(0)
-    name = ctypes.create_string_buffer(96); ms = ctypes.c_double(); cnt = ctypes.c_int(); fl = ctypes.c_double(); by = ctypes.c_double()
-    rows = {}
-    for i in range(lib.xp_prof_count()):
-        lib.xp_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by))
-        rows[name.value.decode()] = {"us": round(ms.value * 1e3, 1), "launches": cnt.value}
-    return dict(sorted(rows.items(), key=lambda kv: -kv[1]["us"]))
-
-
 def bench(shape, iters):
     B, H, W, C = shape
     torch.manual_seed(0)                                     # the block's initialisation: the same weights in every run
@@ -100,13 +67,7 @@ def bench(shape, iters):
     step_hip = run("hip", hip, hip)
     step_eager = run("eager", eager, lambda x: eager_forward(eager, x))
     res = {"shape": list(shape), "rows": B * H * W, "iters": iters, "route_tensor_MiB": round(B * 4 * C * H * W * 4 / 2**20, 1)}
-    for rep in range(2):                                     # alternate: hip, eager, hip, eager
-        for tag, st in (("hip", step_hip), ("eager", step_eager)):
-            ms, mib = measure(st, iters)
-            res.setdefault(f"{tag}_fwd_bwd_ms", []).append(round(ms, 4))
-            res[f"{tag}_peak_MiB"] = round(mib, 1)
-            res[f"{tag}_host_issue_ms"] = round(measure.host_ms, 4)
-    res["ratio_hip_over_eager"] = round(min(res["hip_fwd_bwd_ms"]) / min(res["eager_fwd_bwd_ms"]), 3)
+    alternate(res, step_hip, step_eager, iters)
     # a sanity figure, not a parity check (tests/test_gpu_vss_training.py is): eager f32 is the other side
     pairs = list(zip(hip.parameters(), eager.parameters())) + [(type("G", (), {"grad": grads["hip"]}), type("G", (), {"grad": grads["eager"]}))]
     res["max_grad_diff_vs_eager_over_scale"] = max(float((a.grad - b.grad).abs().max() / b.grad.abs().max().clamp(min=1e-30)) for a, b in pairs)
