@@ -722,7 +722,8 @@ int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, float* dx, int6
  *   NULL: S is taken here from the largest magnitude of dy (max|dy| S in [2^13, 2^14)) and a scaled copy in the workspace is what the engine reads,
  *   so any finite gradient range is accepted.  dx is the UNSCALED gradient (1 / S is applied, exactly, by the epilogue).  Co % 4 == 0 (the engine
  *   loads dy in 4-element channel groups); |w| is unrestricted (row scales of the offline split).  Workspace:
- *   xp_conv3x3_dgrad_h2_workspace_bytes, 256-byte aligned.  Reflection-padded and stride-2 convolutions get no input gradient in this build.
+ *   xp_conv3x3_dgrad_h2_workspace_bytes, 256-byte aligned.  The reflection-padded convolution gets no input gradient in this build; the
+ *   stride-2 one has xp_conv3x3_s2_dgrad_h2, below.
  * xp_relu_fwd: y = max(x, 0) over n elements.  xp_relu_bwd: dy = dr where y > 0, else 0 (y the ReLU's input or its output).
  * xp_maxpool2_relu_bwd: backward of MaxPool2d(2) over ReLU(y), y (batch, H, W, C) the BatchNorm output, dpool (batch, H / 2, W / 2, C):
  *   dy = dpool of the window at the FIRST position, in row-major order inside the window, that attains the window's maximum, provided the maximum is
@@ -782,6 +783,42 @@ int xp_dwconv3x3_silu_bwd(const float* x, const float* w9c, const float* dy, flo
 int xp_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
 int xp_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, float* dx_scale, void* workspace, size_t workspace_bytes, void* stream);
 int xp_add_scaled_rows(const float* x, const float* r, const float* s, float* y, int batch, int64_t rows_per_sample, int C, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training of the whole VMamba encoder (xpoint_amd/training/encoder.py VSSEncoder; csrc/train_dense.hip, csrc/elementwise.hip; DESIGN.md section 19;
+ * reference VMamba.py:1405-1440 patch embed and downsample v3, :1507-1525 VSSM.forward): the strided layers between the VSS blocks.  The convolution
+ * is 3x3, ZERO padding 1, STRIDE 2: x (batch, H, W, Ci), y / dy (batch, Ho, Wo, Co) with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, w (Co, 3, 3, Ci).
+ *
+ * xp_conv3x3_s2_wgrad_h2: dw (Co, 3, 3, Ci): tap (ky, kx) of output pixel (yo, xo) reads x at (2 yo + ky - 1, 2 xo + kx - 1) and contributes 0 outside
+ *   the image.  A stride mode of the kernel of xp_conv3x3_wgrad_h2 with the rest of its contract: XP_WGRAD_CHUNK row chunks added in chunk order,
+ *   dy_scale NULL or {S, 1 / S}, workspace xp_gemm_tn_h2_workspace_bytes(batch Ho Wo, Co, 9 Ci), bit-equal to xp_gemm_tn_h2 on the materialised
+ *   stride-2 im2col matrix.  H, W >= 1, any Ci.
+ * xp_conv3x3_s2_dgrad_h2: the input gradient dx (batch, H, W, Ci) from dy (batch, Ho, Wo, Co) and w; H and W are the caller's (Ho does not determine
+ *   H).  A transposed convolution as FOUR implicit GEMMs on the split-fp16 engine, one per parity class of the dx pixel (y, x): a pixel receives
+ *   only the taps with y + 1 - ky and x + 1 - kx even, from dy at ((y + 1 - ky) / 2, (x + 1 - kx) / 2), which is 1, 2, 2 or 4 taps; a class's
+ *   reduction length is its taps x Co over its slice of one rearranged weight that xp_split_weights_h2 splits once per call.  No zero-stuffed copy of
+ *   dy and no products with structural zeros.  Co % 16 == 0 with a dy below 2 GB runs the row-stationary form (a k-step lies inside one tap, so the
+ *   tap and channel advance as scalars and a pixel's geometry is worked out once per tap), anything else the tile-engine form; both walk K in the same
+ *   order and give the same bits.  The summation order is fixed (taps in (ky, kx) order, channels ascending), no atomics: two calls are
+ *   bit-identical and a sample's dx does not depend on its batch neighbours (given dy_scale).  Scale contract of xp_conv3x3_dgrad_h2: dy_scale NULL:
+ *   S is taken here and a scaled copy of dy in the workspace is what the engine reads; else dy already holds S x the gradient; dx is the unscaled
+ *   gradient (1 / S applied exactly); any finite range.  Co % 4 == 0, dy 16-byte aligned.  Workspace: xp_conv3x3_s2_dgrad_h2_workspace_bytes, 256-byte
+ *   aligned.
+ * xp_stem_conv: the stem's convolution alone (1 -> Co channels, w9co (9, Co) the weight folded over the three identical input channels, + bias), the
+ *   device definition xp_stem_conv_ln_gelu fuses with its LayerNorm and GELU (csrc/glue_core.h): xp_stem_conv -> xp_layernorm -> xp_gelu_fwd is the
+ *   training forward.  f32 only (xp_set_amp_mode is not looked at); Co 48 or 16.
+ * xp_stem_conv_wgrad: dw9co[t][co] = sum_{b,yo,xo} dy[b, yo, xo, co] img[b, 2 yo + ky - 1, 2 xo + kx - 1] in the fixed order and with the f64
+ *   accumulators of xp_colsum_rows; dy_scale != NULL: the sums are multiplied by dy_scale[1].  The bias gradient is xp_colsum_rows; the image gets
+ *   no gradient.  Workspace: xp_stem_conv_wgrad_workspace_bytes(Co). */
+int xp_conv3x3_s2_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_conv3x3_s2_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co);
+int xp_conv3x3_s2_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int xp_stem_conv(const float* img, const float* w9co, const float* bias, float* y, int batch, int H, int W, int Co, void* stream);
+size_t xp_stem_conv_wgrad_workspace_bytes(int Co);
+int xp_stem_conv_wgrad(const float* img, const float* dy, float* dw9co, int batch, int H, int W, int Co, const float* dy_scale, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the

@@ -144,6 +144,10 @@ _SIGNATURES = {
     "xp_gelu_fwd": [c_p, c_p, c_l, c_p],
     "xp_gelu_bwd": [c_p, c_p, c_p, c_l, c_p, c_p, c_sz, c_p],
     "xp_add_scaled_rows": [c_p] * 4 + [c_i, c_l, c_i, c_p],
+    "xp_conv3x3_s2_wgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
+    "xp_conv3x3_s2_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
+    "xp_stem_conv": [c_p] * 4 + [c_i] * 4 + [c_p],
+    "xp_stem_conv_wgrad": [c_p] * 3 + [c_i] * 4 + [c_p, c_p, c_sz, c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -190,6 +194,8 @@ _SIZE_QUERIES = {
     "xp_scale_grad_workspace_bytes": (c_sz, []),
     "xp_layernorm_bwd_workspace_bytes": (c_sz, [c_l, c_i]),
     "xp_dwconv3x3_silu_bwd_workspace_bytes": (c_sz, [c_i] * 4),
+    "xp_conv3x3_s2_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
+    "xp_stem_conv_wgrad_workspace_bytes": (c_sz, [c_i]),
 }
 
 

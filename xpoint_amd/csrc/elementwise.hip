@@ -147,6 +147,12 @@ __global__ __launch_bounds__(64) void stem_conv_ln_gelu_kernel(const float* __re
     xp_stem_conv_ln_gelu_body<CO, float, AMP>(img, w9, bias, lnw, lnb, y, B, H, W, eps);
 }
 
+template <int CO>
+__global__ __launch_bounds__(64) void stem_conv_kernel(const float* __restrict__ img, const float* __restrict__ w9, const float* __restrict__ bias,
+                                                       float* __restrict__ y, int B, int H, int W) {
+    xp_stem_conv_body<CO>(img, w9, bias, y, B, H, W);
+}
+
 // ---------------------------------------------------------------------------------------------
 // depth_to_space(4) in NHWC: out[n, bs*h+i, bs*w+j, c] = x[n, h, w, (bs*i+j)*Cq + c]  (VMamba.py:1500-1505;
 // block-major channel order, NOT PixelShuffle order).
@@ -423,6 +429,21 @@ extern "C" int xp_stem_conv_ln_gelu(const float* img, const float* w9co, const f
     else if (Co == 48) hipLaunchKernelGGL((stem_conv_ln_gelu_kernel<48, false>), grid, block, 0, s, img, w9co, bias, ln_w, ln_b, y, batch, H, W, eps);
     else if (Co == 16) hipLaunchKernelGGL((stem_conv_ln_gelu_kernel<16, false>), grid, block, 0, s, img, w9co, bias, ln_w, ln_b, y, batch, H, W, eps);
     else { xp_set_error("xp_stem_conv_ln_gelu: Co must be 48 or 16 (EMBED_DIM 96 / 32), got %d", Co); return XP_ERR_ARG; }
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+extern "C" int xp_stem_conv(const float* img, const float* w9co, const float* bias, float* y, int batch, int H, int W, int Co, void* stream) {
+    XP_CHECK_ARG(img && w9co && bias && y, "xp_stem_conv: null pointer");
+    XP_CHECK_ARG(batch > 0 && H >= 1 && W >= 1, "xp_stem_conv: bad shape batch=%d H=%d W=%d", batch, H, W);
+    const int Ho = H / 2 + (H & 1), Wo = W / 2 + (W & 1);
+    const int64_t total = (int64_t)batch * Ho * Wo;
+    dim3 grid(xp_cdiv(total, 64)), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    XpProfScope prof("stem_conv", s, (double)total * Co * 18.0, 4.0 * ((double)batch * H * W + (double)total * Co));
+    if (Co == 48) hipLaunchKernelGGL(stem_conv_kernel<48>, grid, block, 0, s, img, w9co, bias, y, batch, H, W);
+    else if (Co == 16) hipLaunchKernelGGL(stem_conv_kernel<16>, grid, block, 0, s, img, w9co, bias, y, batch, H, W);
+    else { xp_set_error("xp_stem_conv: Co must be 48 or 16 (EMBED_DIM 96 / 32), got %d", Co); return XP_ERR_ARG; }
     XP_LAUNCH_CHECK();
     return XP_OK;
 }

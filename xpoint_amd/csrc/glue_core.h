@@ -125,6 +125,32 @@ __device__ __forceinline__ void xp_dwconv3x3_silu_body(const T* __restrict__ x, 
 // CO + 2 halves) for coalesced stores.
 // ---------------------------------------------------------------------------------------------
 // R16: the image is cast to half by autocast's convolution, and conv, LayerNorm and GELU each return a half tensor
+// The stem's convolution of ONE output pixel: acc[c] = bias[c] + sum_t x[t] w[t][c] (s_w: [tap][CO], the bias in row 9), returns sum_c acc[c].  The fused
+// kernel below and the training forward's xp_stem_conv share it: one summation order, the same bits.
+template <int CO, bool R16>
+__device__ __forceinline__ float xp_stem_conv_pixel(const float* __restrict__ img, const float* s_w, int64_t b, int oh, int ow, int H, int W, float (&acc)[CO]) {
+    float xin[9];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
+            xin[kh * 3 + kw] = (ih >= 0 && ih < H && iw >= 0 && iw < W) ? img[(b * H + ih) * W + iw] : 0.f;
+            if (R16) xin[kh * 3 + kw] = xp_r16(xin[kh * 3 + kw]);
+        }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CO; ++c) {
+        float a = 0.f;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) a = fmaf(xin[t], s_w[t * CO + c], a);
+        a += s_w[9 * CO + c];
+        if (R16) a = xp_r16(a);
+        acc[c] = a; s += a;
+    }
+    return s;
+}
+
 template <int CO, typename T, bool R16>
 __device__ __forceinline__ void xp_stem_conv_ln_gelu_body(const float* __restrict__ img, const float* __restrict__ w9, const float* __restrict__ bias,
                                                           const float* __restrict__ lnw, const float* __restrict__ lnb, T* __restrict__ y,
@@ -143,26 +169,8 @@ __device__ __forceinline__ void xp_stem_conv_ln_gelu_body(const float* __restric
     if (pix < total) {
         const int ow = (int)(pix % Wo), oh = (int)((pix / Wo) % Ho);
         const int64_t b = pix / ((int64_t)Wo * Ho);
-        float xin[9];
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
-                xin[kh * 3 + kw] = (ih >= 0 && ih < H && iw >= 0 && iw < W) ? img[(b * H + ih) * W + iw] : 0.f;
-                if (R16) xin[kh * 3 + kw] = xp_r16(xin[kh * 3 + kw]);
-            }
         float acc[CO];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < CO; ++c) {
-            float a = 0.f;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) a = fmaf(xin[t], s_w[t * CO + c], a);
-            a += s_w[9 * CO + c];
-            if (R16) a = xp_r16(a);
-            acc[c] = a; s += a;
-        }
+        const float s = xp_stem_conv_pixel<CO, R16>(img, s_w, b, oh, ow, H, W, acc);
         const float mean = s / (float)CO;
         float q = 0.f;
 #pragma unroll
@@ -176,6 +184,36 @@ __device__ __forceinline__ void xp_stem_conv_ln_gelu_body(const float* __restric
             if (R16) v = xp_r16(v);
             s_o[threadIdx.x * LDO + c] = (T)v;
         }
+    }
+    __syncthreads();
+    const int64_t nvalid = (total - p0 < 64) ? (total - p0) : 64;
+    for (int i = threadIdx.x; i < nvalid * CO; i += 64) {
+        const int pl = i / CO, c = i - pl * CO;
+        y[(p0 + pl) * CO + c] = s_o[pl * LDO + c];
+    }
+}
+
+// The stem's convolution alone (f32): what the training forward keeps as the LayerNorm's input.  Same staging as the fused body.
+template <int CO>
+__device__ __forceinline__ void xp_stem_conv_body(const float* __restrict__ img, const float* __restrict__ w9, const float* __restrict__ bias,
+                                                  float* __restrict__ y, int B, int H, int W) {
+    constexpr int LDO = CO + 1;
+    __shared__ float s_w[10 * CO];
+    __shared__ float s_o[64 * LDO];
+    for (int i = threadIdx.x; i < 9 * CO; i += 64) s_w[i] = w9[i];
+    for (int i = threadIdx.x; i < CO; i += 64) s_w[9 * CO + i] = bias[i];
+    __syncthreads();
+    const int Ho = H / 2 + (H & 1), Wo = W / 2 + (W & 1);
+    const int64_t total = (int64_t)B * Ho * Wo;
+    const int64_t p0 = (int64_t)blockIdx.x * 64;
+    const int64_t pix = p0 + threadIdx.x;
+    if (pix < total) {
+        const int ow = (int)(pix % Wo), oh = (int)((pix / Wo) % Ho);
+        const int64_t b = pix / ((int64_t)Wo * Ho);
+        float acc[CO];
+        (void)xp_stem_conv_pixel<CO, false>(img, s_w, b, oh, ow, H, W, acc);
+#pragma unroll
+        for (int c = 0; c < CO; ++c) s_o[threadIdx.x * LDO + c] = acc[c];
     }
     __syncthreads();
     const int64_t nvalid = (total - p0 < 64) ? (total - p0) : 64;

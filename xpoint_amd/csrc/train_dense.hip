@@ -1,6 +1,7 @@
 // Dense backward kernels of head training: the weight-gradient GEMM on the split-fp16 matrix path, its implicit 3x3 form,
 // BatchNorm training forward / backward over NHWC rows, the column sums behind the bias gradients and the L2-normalise backward; at the end of the
-// file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head, and xp_scale_grad, the amax / power-of-two
+// file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head, the same two for the STRIDE-2 convolutions
+// of patch embed and the downsamplers with the stem's weight gradient (encoder training), and xp_scale_grad, the amax / power-of-two
 // / scale kernels of the weight gradient as an entry point of their own (VSS-block training).  The row walks and the fixed-order column sums
 // are in train_rows.h, which train_vss.hip shares.
 //
@@ -73,11 +74,13 @@ struct WgParams {
     int M, I, J, ldp, ldq;
     int prescaled;           // P already holds S x the gradient
     int H, W, Ci;
+    int Ho, Wo;              // CONV 3: the output grid the rows of P walk (stride 2)
 };
 
 __device__ __forceinline__ int td_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-// CONV: 0 = Q is a matrix, 1 = the im2col view under reflection padding, 2 = under zero padding (a tap outside the image contributes 0)
+// CONV: 0 = Q is a matrix, 1 = the im2col view under reflection padding, 2 = under zero padding (a tap outside the image contributes 0),
+// 3 = zero padding at STRIDE 2: row m is output pixel (yo, xo) of the (Ho, Wo) grid and tap (ky, kx) reads x at (2 yo + ky - 1, 2 xo + kx - 1)
 template <int CONV>
 __global__ __launch_bounds__(256) void td_wgrad_kernel(const WgParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * WG_BT * H2_ROWB];
@@ -109,7 +112,8 @@ __global__ __launch_bounds__(256) void td_wgrad_kernel(const WgParams p) {
             const int mc = mok ? m : m_begin;                                  // a valid row: the load is unconditional, the value is selected
             const float* pr = p.P + (int64_t)mc * p.ldp + i0 + 4 * cq;
             int b = 0, y = 0, x = 0;
-            if (CONV) { b = mc / (p.H * p.W); const int rem = mc - b * p.H * p.W; y = rem / p.W; x = rem - y * p.W; }
+            if (CONV == 3) { b = mc / (p.Ho * p.Wo); const int rem = mc - b * p.Ho * p.Wo; y = rem / p.Wo; x = 2 * (rem - y * p.Wo); y *= 2; }
+            else if (CONV) { b = mc / (p.H * p.W); const int rem = mc - b * p.H * p.W; y = rem / p.W; x = rem - y * p.W; }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float pv = pr[pok[e] ? e : -(4 * cq)];                 // columns past I read the tile's first column, which exists
@@ -119,7 +123,7 @@ __global__ __launch_bounds__(256) void td_wgrad_kernel(const WgParams p) {
                 if (CONV == 1) {
                     const int yy = td_reflect(y + qky[e], p.H), xx = td_reflect(x + qkx[e], p.W);
                     qv = p.Q[(((int64_t)b * p.H + yy) * p.W + xx) * p.Ci + qci[e]];
-                } else if (CONV == 2) {
+                } else if (CONV >= 2) {
                     const int ty = y + qky[e], tx = x + qkx[e];
                     tap = ty >= 0 && ty < p.H && tx >= 0 && tx < p.W;
                     const int yy = min(max(ty, 0), p.H - 1), xx = min(max(tx, 0), p.W - 1);      // a valid address: the load is unconditional, the value is selected
@@ -216,9 +220,10 @@ static int td_wgrad_launch(const char* who, int conv, WgParams p, float* out, in
     const dim3 grid(xp_cdiv(p.J, WG_BT), xp_cdiv(p.I, WG_BT), nchunk);
     XP_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "%s: shape too large", who);
     {
-        XpProfScope prof(conv == 2 ? "conv3x3_zp_wgrad_h2" : conv ? "conv3x3_wgrad_h2" : "gemm_tn_h2", s, 6.0 * p.M * p.I * p.J, 4.0 * p.M * (p.I + p.J));
+        XpProfScope prof(conv == 3 ? "conv3x3_s2_wgrad_h2" : conv == 2 ? "conv3x3_zp_wgrad_h2" : conv ? "conv3x3_wgrad_h2" : "gemm_tn_h2", s, 6.0 * p.M * p.I * p.J, 4.0 * p.M * (p.I + p.J));
         if (conv == 1) hipLaunchKernelGGL(td_wgrad_kernel<1>, grid, dim3(256), 0, s, p);
         else if (conv == 2) hipLaunchKernelGGL(td_wgrad_kernel<2>, grid, dim3(256), 0, s, p);
+        else if (conv == 3) hipLaunchKernelGGL(td_wgrad_kernel<3>, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(td_wgrad_kernel<0>, grid, dim3(256), 0, s, p);
         XP_LAUNCH_CHECK();
     }
@@ -523,6 +528,330 @@ extern "C" int xp_conv3x3_dgrad_h2(const float* dy, const float* w, float* dx, i
     XP_TRY(xp_split_weights_h2(wrot, ws + l.wsplit, Ci, 9 * Co, stream));
     // dx = conv3x3(zero_pad(S dy), wrot) / S on the forward's implicit-GEMM engine: no atomics, the engine's fixed summation order
     return xp_conv3x3_nhwc_h2(dy, ws + l.wsplit, dx, nullptr, vscale, vshift, batch, H, W, Co, Ci, 1, 0, 0, stream);
+}
+
+// ---- the zero-padded STRIDE-2 3x3 convolution of patch embed and the downsamplers (VMamba.py:1405-1440): weight gradient, input gradient ----
+// Input gradient.  dx pixel (y, x) receives tap (ky, kx) only when y + 1 - ky and x + 1 - kx are even, from dy at ((y + 1 - ky) / 2, (x + 1 - kx) / 2):
+// the pixels fall into four classes by the parity (py, px) of (y, x) with (1 + py)(1 + px) = 1, 2, 2, 4 taps — ky = 1 for an even y, ky = 0 (dy row
+// i + 1) and ky = 2 (dy row i) for the odd y = 2 i + 1, the same along x.  Each class is an implicit GEMM of its own on the split-fp16 engine:
+// M = its pixels, N = Ci, K = taps Co, the A row of a pixel gathered from dy tap by tap, the weight a K-slice of ONE rearranged (Ci, Ktot) matrix that
+// is split once per call (every class's slice padded to whole 32-wide slabs).  No zero-stuffed dy, no products with structural zeros.
+namespace {
+
+struct S2Class { int py, px, Hc, Wc, taps, slab0, nslab; };
+static S2Class td_s2_class(int c, int H, int W, int Co) {
+    S2Class k{};
+    k.py = c >> 1; k.px = c & 1;
+    k.Hc = (H + 1 - k.py) / 2; k.Wc = (W + 1 - k.px) / 2;
+    k.taps = (1 + k.py) * (1 + k.px);
+    for (int q = 0; q <= c; ++q) {
+        const int n = xp_cdiv((1 + (q >> 1)) * (1 + (q & 1)) * Co, H2_BK);
+        if (q < c) k.slab0 += n; else k.nslab = n;
+    }
+    return k;
+}
+static int td_s2_ktot(int Co) { const S2Class k = td_s2_class(3, 1, 1, Co); return (k.slab0 + k.nslab) * H2_BK; }
+
+// wc[ci][32 slab0(c) + (ty nx + tx) Co + co] = w[co][ky][kx][ci], ky = py ? 2 ty : 1, kx = px ? 2 tx : 1; zeros in the pad of every slice
+__global__ __launch_bounds__(256) void td_s2_weights_kernel(const float* __restrict__ w, float* __restrict__ wc, int Ci, int Co, int Ktot) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Ci * Ktot) return;
+    const int ci = idx / Ktot;
+    int k = idx - ci * Ktot;
+    float v = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int py = c >> 1, px = c & 1, taps = (1 + py) * (1 + px), span = (taps * Co + H2_BK - 1) / H2_BK * H2_BK;
+        if (k >= 0 && k < taps * Co) {
+            const int tap = k / Co, co = k - tap * Co;
+            const int ty = px ? tap >> 1 : tap, tx = px ? tap & 1 : 0;
+            v = w[((int64_t)co * 9 + (py ? 2 * ty : 1) * 3 + (px ? 2 * tx : 1)) * Ci + ci];
+        }
+        k = k < 0 ? k : (k < span ? -1 : k - span);          // consumed by this class, or moved on to the next
+    }
+    wc[idx] = v;
+}
+
+struct S2DgParams {
+    const float* dy;         // S x the gradient, (batch, Ho, Wo, Co)
+    const uint4* wsplit;     // xp_split_weights_h2 of wc (Ci, Ktot)
+    const float* wscale;     // its Ci inverse row scales
+    const float2* scale;     // {S, 1 / S}
+    float* dx;               // (batch, H, W, Ci)
+    int batch, H, W, Ci, Co, Ho, Wo;
+    int slab0[4];            // first slab of class c's K-slice
+};
+
+// row m of class (py, px) is dx pixel (2 i + py, 2 j + px) of sample b: dx = accumulator x the weight row's power of two x 1 / S, both exact
+template <class T, int TN>
+__device__ __forceinline__ void td_s2_store(const S2DgParams& p, const f32x16 (&acc)[1][TN], int m0, int n0, int Mc, int Hc, int Wc, int py, int px) {
+    const float inv_s = p.scale->y;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m0 + T::row_of(0, r);
+        if (m >= Mc) continue;
+        const int b = m / (Hc * Wc), rr = m - b * (Hc * Wc), i = rr / Wc, j = rr - i * Wc;
+        float* row = p.dx + (((int64_t)b * p.H + 2 * i + py) * p.W + 2 * j + px) * p.Ci;
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) {
+            const int n = n0 + T::col_of(jn);
+            if (n < p.Ci) row[n] = acc[0][jn][r] * p.wscale[n] * inv_s;
+        }
+    }
+}
+
+template <int TN>
+__global__ __launch_bounds__(256) void td_s2_dgrad_kernel(const S2DgParams p) {
+    using T = GemmTileH2<2, 2, 1, TN>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[T::kLdsBytes];
+    const int cls = blockIdx.z, py = cls >> 1, px = cls & 1;
+    const int Hc = (p.H + 1 - py) / 2, Wc = (p.W + 1 - px) / 2;
+    const int Mc = p.batch * Hc * Wc, Kc = (1 + py) * (1 + px) * p.Co;
+    const int m0 = blockIdx.x * T::BM, n0 = blockIdx.y * T::BN;
+    if (m0 >= Mc) return;                          // block-uniform, before any barrier: this class has fewer row tiles (or no pixel at all)
+
+    const float* a_ptr[T::A_LD];
+    int a_i[T::A_LD], a_j[T::A_LD], a_tap[T::A_LD], a_co[T::A_LD];
+#pragma unroll
+    for (int s = 0; s < T::A_LD; ++s) {
+        const int m = m0 + T::a_row(s);
+        const int mc = m < Mc ? m : 0;           // rows past Mc only feed output rows that are never stored
+        const int b = mc / (Hc * Wc), rr = mc - b * (Hc * Wc);
+        a_i[s] = rr / Wc; a_j[s] = rr - a_i[s] * Wc;
+        a_ptr[s] = p.dy + (int64_t)b * p.Ho * p.Wo * p.Co;
+        const int k = T::a_quad(s) * 4;          // (tap, co) advance by one slab per call: no division in the K loop
+        a_tap[s] = k / p.Co; a_co[s] = k - a_tap[s] * p.Co;
+    }
+    const int nslab = (Kc + H2_BK - 1) / H2_BK;
+    const uint4* w_unit[T::B_LD];
+#pragma unroll
+    for (int s = 0; s < T::B_LD; ++s) {
+        const int n = n0 + T::b_row(s);
+        w_unit[s] = p.wsplit + (int64_t)(n < p.Ci ? n : 0) * H2_SLAB_UNITS + T::b_unit(s);
+    }
+    const int64_t w_slab = (int64_t)p.Ci * H2_SLAB_UNITS;
+    const int slab0 = p.slab0[cls];
+    auto ldA = [&](int s, int k, float4& v) -> bool {
+        bool ok = k < Kc;
+        int tap = a_tap[s], co = a_co[s];
+        if (!ok) { tap = 0; co = 0; }
+        a_co[s] += H2_BK;                                  // Co >= 4: at most eight wraps per 32-wide slab, as selects
+#pragma unroll
+        for (int w = 0; w < 8; ++w) { const bool wrap = a_co[s] >= p.Co; a_co[s] -= wrap ? p.Co : 0; a_tap[s] += wrap ? 1 : 0; }
+        const int ty = px ? tap >> 1 : tap, tx = px ? tap & 1 : 0;
+        int yo = a_i[s] + ((py && ty == 0) ? 1 : 0), xo = a_j[s] + ((px && tx == 0) ? 1 : 0);      // never negative
+        ok = ok && yo < p.Ho && xo < p.Wo;
+        yo = yo < p.Ho ? yo : p.Ho - 1; xo = xo < p.Wo ? xo : p.Wo - 1;      // a valid address: the load is unconditional, the slot is staged as zeros
+        v = *reinterpret_cast<const float4*>(a_ptr[s] + ((int64_t)yo * p.Wo + xo) * p.Co + co);
+        return ok;
+    };
+    auto ldB = [&](int s, int t) -> uint4 { return w_unit[s][(slab0 + (t < nslab ? t : nslab - 1)) * w_slab]; };
+
+    f32x16 acc[1][TN];
+    T::run(lds, Kc, ldA, ldB, acc);
+
+    td_s2_store<T, TN>(p, acc, m0, n0, Mc, Hc, Wc, py, px);
+}
+
+// The same GEMMs on the row-stationary engine (GemmTileH2R: every lane loads its own row's fragment straight from global memory, only the weights go
+// through the LDS), for Co % 16 == 0 and a dy below 2 GB: a 16-wide k-step then lies inside ONE tap, the same for the whole wave, so (tap, co) advance as
+// scalars and the lane's geometry — which dy pixel the tap reads, whether it exists — is worked out once per tap, at most four times per launch, as a
+// 32-bit byte offset into a buffer resource over dy; a tap outside dy and a k-step past the class's K carry an offset beyond its end and the hardware
+// returns zeros (the scheme of gemm_h2r_kernel's convolution form).  Same values in the same order as the tile-engine form above: the same bits.
+template <int TN>
+__global__ __launch_bounds__(256) void td_s2_dgrad_r_kernel(const S2DgParams p) {
+    using T = GemmTileH2R<TN>;
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int cls = blockIdx.z, py = cls >> 1, px = cls & 1;
+    const int Hc = (p.H + 1 - py) / 2, Wc = (p.W + 1 - px) / 2;
+    const int Mc = p.batch * Hc * Wc, taps = (1 + py) * (1 + px), Kc = taps * p.Co;
+    const int m0 = blockIdx.x * T::BM, n0 = blockIdx.y * T::BN;
+    if (m0 >= Mc) return;                          // block-uniform, before any barrier
+
+    const int fh = (threadIdx.x & 63) >> 5;
+    const int m = m0 + T::a_row();
+    const int mc = m < Mc ? m : 0;               // rows past Mc only feed output rows that are never stored
+    const int b = mc / (Hc * Wc), rr = mc - b * (Hc * Wc), ai = rr / Wc, aj = rr - ai * Wc;
+    const int nslab = (Kc + H2_BK - 1) / H2_BK;
+    const uint4* w_unit[T::B_LD];
+#pragma unroll
+    for (int s = 0; s < T::B_LD; ++s) {
+        const int n = n0 + T::b_row(s);
+        w_unit[s] = p.wsplit + (int64_t)(n < p.Ci ? n : 0) * H2_SLAB_UNITS + T::b_unit(s);
+    }
+    const int64_t w_slab = (int64_t)p.Ci * H2_SLAB_UNITS;
+    const int slab0 = p.slab0[cls];
+    auto ldB = [&](int s, int t) -> uint4 { return w_unit[s][(slab0 + (t < nslab ? t : nslab - 1)) * w_slab]; };
+
+    constexpr unsigned kPastEnd = 0x80000000u;                 // >= the bytes of dy (the host checks), and no 32-bit wrap when the channel offset is added
+    const unsigned dy_bytes = (unsigned)p.batch * p.Ho * p.Wo * p.Co * 4u;
+    const unsigned lane_base = (unsigned)b * p.Ho * p.Wo * p.Co * 4u + (unsigned)fh * 32u;       // the lane's sample and its half of the k-step
+    auto tap_offset = [&](int tap) -> unsigned {
+        if (tap >= taps) return kPastEnd;
+        const int ty = px ? tap >> 1 : tap, tx = px ? tap & 1 : 0;
+        const int yo = ai + ((py && ty == 0) ? 1 : 0), xo = aj + ((px && tx == 0) ? 1 : 0);      // never negative
+        return (yo < p.Ho && xo < p.Wo) ? lane_base + (unsigned)((yo * p.Wo + xo) * p.Co) * 4u : kPastEnd;
+    };
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (int)dy_bytes, 0x00020000);
+    int tap = 0, co4 = 0;                                       // of the next k-step: wave-uniform (co4 = byte offset of its first channel)
+    unsigned cur = tap_offset(0);
+    typedef unsigned raw4 __attribute__((ext_vector_type(4)));
+    auto ldA8 = [&](int, float4& lo, float4& hi) -> bool {
+        const raw4 a = __builtin_bit_cast(raw4, __builtin_amdgcn_raw_buffer_load_b128(rs, cur, co4, 0));
+        const raw4 c = __builtin_bit_cast(raw4, __builtin_amdgcn_raw_buffer_load_b128(rs, cur + 16, co4, 0));
+        lo = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
+        hi = make_float4(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w));
+        co4 += 64;
+        if (co4 == p.Co * 4) { co4 = 0; ++tap; cur = tap_offset(tap); }
+        return true;
+    };
+    f32x16 acc[1][TN];
+    T::template run<false>(lds, Kc, ldA8, ldB, acc);
+
+    td_s2_store<T, TN>(p, acc, m0, n0, Mc, Hc, Wc, py, px);
+}
+
+template <int TN>
+static int td_s2_dgrad_r_launch(const S2DgParams& p, int64_t m_even, hipStream_t s) {
+    using T = GemmTileH2R<TN>;
+    hipLaunchKernelGGL(td_s2_dgrad_r_kernel<TN>, dim3((unsigned)xp_cdiv(m_even, (int64_t)T::BM), xp_cdiv(p.Ci, T::BN), 4), dim3(256), T::kLdsBytes, s, p);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+template <int TN>
+static int td_s2_dgrad_launch(const S2DgParams& p, int64_t m_even, hipStream_t s) {
+    using T = GemmTileH2<2, 2, 1, TN>;
+    hipLaunchKernelGGL(td_s2_dgrad_kernel<TN>, dim3((unsigned)xp_cdiv(m_even, (int64_t)T::BM), xp_cdiv(p.Ci, T::BN), 4), dim3(256), 0, s, p);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+struct S2DgradLayout { size_t wc, wsplit, dys, total; };
+static S2DgradLayout td_s2_dgrad_layout(int batch, int Ho, int Wo, int Ci, int Co) {
+    S2DgradLayout l{};
+    const int Ktot = td_s2_ktot(Co);
+    l.wc = WG_HEAD_BYTES;                                                    // head: partial maxima and {S, 1 / S}, as the weight gradient's
+    l.wsplit = l.wc + td_up256((size_t)Ci * Ktot * sizeof(float));
+    l.dys = l.wsplit + td_up256(xp_split_weights_h2_bytes(Ci, Ktot));
+    l.total = l.dys + td_up256((size_t)batch * Ho * Wo * Co * sizeof(float));
+    return l;
+}
+static bool td_s2_shape_ok(int batch, int H, int W, int Ci, int Co) {
+    return batch > 0 && H >= 1 && W >= 1 && Ci > 0 && Co > 0 && (int64_t)batch * H * W < ((int64_t)1 << 31) / 16 && (int64_t)Ci * Co < (1 << 24);
+}
+
+// dw9co[t][co] = sum over output pixels of dy[b, yo, xo, co] img[b, 2 yo + ky - 1, 2 xo + kx - 1]: the 9 Co sums of the stem in the fixed order of the
+// BatchNorm sums (train_rows.h), f64 accumulators
+__global__ __launch_bounds__(256) void td_stem_wgrad_parts_kernel(const float* __restrict__ img, const float* __restrict__ dy, int H, int W, int Ho, int Wo,
+                                                                  int64_t rows, int Co, double* __restrict__ part) {
+    td_colsum_parts<9>(rows, Co, part, [&](int64_t r, int c, double (&a)[9]) {
+        const int64_t b = r / ((int64_t)Ho * Wo);
+        const int rem = (int)(r - b * Ho * Wo), yo = rem / Wo, xo = rem - yo * Wo;
+        const double g = (double)dy[r * Co + c];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int ih = 2 * yo + t / 3 - 1, iw = 2 * xo + t % 3 - 1;
+            const bool in = ih >= 0 && ih < H && iw >= 0 && iw < W;
+            const float v = img[(b * H + (in ? ih : 0)) * W + (in ? iw : 0)];
+            a[t] += in ? g * (double)v : 0.0;
+        }
+    });
+}
+__global__ __launch_bounds__(256) void td_stem_wgrad_finish_kernel(const double* __restrict__ part, int Co, const float2* __restrict__ scale,
+                                                                   float* __restrict__ out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 9 * Co) return;
+    const int t = idx / Co, c = idx - t * Co;
+    const float s = (float)td_sum_parts(part, 9, t, Co, c);
+    out[idx] = scale ? s * scale->y : s;
+}
+static size_t td_stem_wgrad_bytes(int Co) { return Co > 0 ? td_up256((size_t)BN_PARTS * 9 * Co * sizeof(double)) : 0; }
+
+}  // namespace
+
+extern "C" int xp_conv3x3_s2_wgrad_h2(const float* x, const float* dy, float* dw, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(x && dy && dw, "xp_conv3x3_s2_wgrad_h2: null pointer");
+    XP_CHECK_ARG(td_s2_shape_ok(batch, H, W, Ci, Co), "xp_conv3x3_s2_wgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d", batch, H, W, Ci, Co);
+    WgParams p{};
+    p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
+    p.P = dy; p.Q = x; p.M = batch * p.Ho * p.Wo; p.I = Co; p.J = 9 * Ci; p.ldp = Co; p.ldq = 0; p.H = H; p.W = W; p.Ci = Ci;
+    return td_wgrad_launch("xp_conv3x3_s2_wgrad_h2", 3, p, dw, 9 * Ci, dy_scale, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t xp_conv3x3_s2_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co) {
+    if (!td_s2_shape_ok(batch, H, W, Ci, Co)) return 0;
+    return td_s2_dgrad_layout(batch, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Ci, Co).total;
+}
+
+extern "C" int xp_conv3x3_s2_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(dy && w && dx, "xp_conv3x3_s2_dgrad_h2: null pointer");
+    XP_CHECK_ARG(td_s2_shape_ok(batch, H, W, Ci, Co), "xp_conv3x3_s2_dgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d", batch, H, W, Ci, Co);
+    XP_CHECK_ARG(Co % 4 == 0, "xp_conv3x3_s2_dgrad_h2: Co must be a multiple of 4 (got %d): the engine loads dy in 4-element channel groups", Co);
+    XP_CHECK_ARG(((uintptr_t)dy & 15) == 0, "xp_conv3x3_s2_dgrad_h2: dy must be 16-byte aligned");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const S2DgradLayout l = td_s2_dgrad_layout(batch, Ho, Wo, Ci, Co);
+    XP_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= l.total,
+                 "xp_conv3x3_s2_dgrad_h2: workspace of %zu bytes, 256-byte aligned, needed (got %zu)", l.total, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const float2* scale = (const float2*)dy_scale;
+    const int64_t rows = (int64_t)batch * Ho * Wo;
+    if (!dy_scale) {          // S from the largest magnitude of dy, and the scaled copy the engine reads
+        float* amax = (float*)ws;
+        float2* own = (float2*)(ws + AMAX_PARTS * 4);
+        float* dys = (float*)(ws + l.dys);
+        const int nb = td_elem_blocks(rows);
+        hipLaunchKernelGGL(td_amax_kernel, dim3(nb), dim3(256), 0, s, dy, rows, Co, Co, amax);
+        XP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(td_scale_kernel, dim3(1), dim3(256), 0, s, amax, nb, own);
+        XP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(td_scaled_copy_kernel, dim3(nb), dim3(256), 0, s, dy, dys, rows, Co, own);
+        XP_LAUNCH_CHECK();
+        scale = own; dy = dys;
+    }
+    const int Ktot = td_s2_ktot(Co);
+    float* wc = (float*)(ws + l.wc);
+    hipLaunchKernelGGL(td_s2_weights_kernel, dim3(xp_cdiv(Ci * Ktot, 256)), dim3(256), 0, s, w, wc, Ci, Co, Ktot);
+    XP_LAUNCH_CHECK();
+    XP_TRY(xp_split_weights_h2(wc, ws + l.wsplit, Ci, Ktot, stream));
+    S2DgParams p{};
+    p.dy = dy; p.wsplit = (const uint4*)(ws + l.wsplit); p.wscale = h2_scales(ws + l.wsplit, Ci, Ktot); p.scale = scale; p.dx = dx;
+    p.batch = batch; p.H = H; p.W = W; p.Ci = Ci; p.Co = Co; p.Ho = Ho; p.Wo = Wo;
+    for (int c = 0; c < 4; ++c) p.slab0[c] = td_s2_class(c, H, W, Co).slab0;
+    const int64_t m_even = (int64_t)batch * ((H + 1) / 2) * ((W + 1) / 2);        // the largest class
+    XpProfScope prof("conv3x3_s2_dgrad_h2", s, 6.0 * rows * 9.0 * Ci * Co, 4.0 * (rows * Co + (double)batch * H * W * Ci));
+    // Row-stationary form where a k-step lies inside one tap and 32-bit offsets reach all of dy; the tile-engine form otherwise.  Both walk K in the same
+    // order, so the choice never changes a result bit (measured at the three downsampler shapes, batch 16: 40 / 42 / 68 us against 65 / 58 / 87 us).
+    if (Co % 16 == 0 && rows * Co * 4 < ((int64_t)1 << 31)) {
+        if (Ci <= 32) return td_s2_dgrad_r_launch<1>(p, m_even, s);
+        if (Ci <= 64) return td_s2_dgrad_r_launch<2>(p, m_even, s);
+        if (Ci <= 96 || Ci % 96 == 0) return td_s2_dgrad_r_launch<3>(p, m_even, s);          // 96, 192, 384: no column of the tile is wasted
+        return td_s2_dgrad_r_launch<4>(p, m_even, s);
+    }
+    return Ci <= 64 ? td_s2_dgrad_launch<1>(p, m_even, s) : td_s2_dgrad_launch<2>(p, m_even, s);
+}
+
+extern "C" size_t xp_stem_conv_wgrad_workspace_bytes(int Co) { return td_stem_wgrad_bytes(Co); }
+
+extern "C" int xp_stem_conv_wgrad(const float* img, const float* dy, float* dw9co, int batch, int H, int W, int Co, const float* dy_scale, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(img && dy && dw9co, "xp_stem_conv_wgrad: null pointer");
+    XP_CHECK_ARG(batch > 0 && H >= 1 && W >= 1 && Co > 0 && Co <= (1 << 16) && (int64_t)batch * H * W < ((int64_t)1 << 31),
+                 "xp_stem_conv_wgrad: bad shape batch=%d H=%d W=%d Co=%d", batch, H, W, Co);
+    XP_CHECK_ARG(workspace && workspace_bytes >= td_stem_wgrad_bytes(Co), "xp_stem_conv_wgrad: workspace of %zu bytes needed", td_stem_wgrad_bytes(Co));
+    hipStream_t s = (hipStream_t)stream;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int64_t rows = (int64_t)batch * Ho * Wo;
+    double* part = (double*)workspace;
+    XpProfScope prof("stem_conv_wgrad", s, 18.0 * rows * Co, 4.0 * rows * (Co + 9));
+    hipLaunchKernelGGL(td_stem_wgrad_parts_kernel, dim3(xp_cdiv(Co, 32), BN_PARTS), dim3(256), 0, s, img, dy, H, W, Ho, Wo, rows, Co, part);
+    XP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(td_stem_wgrad_finish_kernel, dim3(xp_cdiv(9 * Co, 256)), dim3(256), 0, s, part, Co, (const float2*)dy_scale, dw9co);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
 }
 
 // ---- one power of two for a gradient that arrives from elsewhere (the block's incoming dy, the scan / cross-scan backward): DESIGN.md §16 ----

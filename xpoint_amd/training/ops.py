@@ -123,6 +123,88 @@ def conv3x3_dgrad(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
     return dx
 
 
+def _s2_out(n):
+    """Output length of the 3x3 stride-2 padding-1 convolution along an axis of n pixels."""
+    return (n - 1) // 2 + 1
+
+
+def conv3x3_s2_wgrad(x_nhwc, dy_nhwc, dy_scale=None, stream=None):
+    """Weight gradient (Co, 3, 3, Ci) of the zero-padded STRIDE-2 3x3 convolution (patch embed, the downsamplers): x (B, H, W, Ci),
+    dy (B, Ho, Wo, Co) with Ho = (H - 1) // 2 + 1, Wo = (W - 1) // 2 + 1, contiguous.  dy_scale as gemm_tn's p_scale."""
+    _check_operands("conv3x3_s2_wgrad", x_nhwc, dy_nhwc, dy_scale)
+    if x_nhwc.dim() != 4 or dy_nhwc.dim() != 4 or min(x_nhwc.shape) < 1 or \
+            tuple(dy_nhwc.shape[:3]) != (x_nhwc.shape[0], _s2_out(x_nhwc.shape[1]), _s2_out(x_nhwc.shape[2])):
+        raise ValueError(f"conv3x3_s2_wgrad: dy {tuple(dy_nhwc.shape)} is not the stride-2 output grid of x {tuple(x_nhwc.shape)}")
+    B, H, W, Ci = x_nhwc.shape
+    Ho, Wo, Co = dy_nhwc.shape[1:]
+    dw = _f32((Co, 3, 3, Ci), x_nhwc.device)
+    ws = _ws(x_nhwc.device, "gemm_tn_h2", B * Ho * Wo, Co, 9 * Ci)
+    _launch("xp_conv3x3_s2_wgrad_h2", x_nhwc, stream, ptr(x_nhwc), ptr(dy_nhwc), ptr(dw), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
+    return dw
+
+
+def conv3x3_s2_dgrad(dy_nhwc, w_ohwi, in_hw, dy_scale=None, stream=None):
+    """Input gradient (B, H, W, Ci) of the zero-padded STRIDE-2 3x3 convolution from dy (B, Ho, Wo, Co) and w (Co, 3, 3, Ci); in_hw = (H, W) of the
+    input (Ho does not determine H).  dy_scale: None, or the device float[2] {S, 1 / S} of a dy that already holds S x the gradient; the result is the
+    unscaled gradient either way.  Co % 4 == 0."""
+    _check_operands("conv3x3_s2_dgrad", dy_nhwc, w_ohwi, dy_scale)
+    H, W = (int(v) for v in in_hw)
+    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3) or H < 1 or W < 1 or \
+            tuple(dy_nhwc.shape[1:3]) != (_s2_out(H), _s2_out(W)):
+        raise ValueError(f"conv3x3_s2_dgrad: dy {tuple(dy_nhwc.shape)} must be (B, Ho, Wo, Co) of in_hw {(H, W)} and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
+    B, _, _, Co = dy_nhwc.shape
+    Ci = w_ohwi.shape[-1]
+    dx = _f32((B, H, W, Ci), dy_nhwc.device)
+    ws = _ws(dy_nhwc.device, "conv3x3_s2_dgrad_h2", B, H, W, Ci, Co)
+    _launch("xp_conv3x3_s2_dgrad_h2", dy_nhwc, stream, ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
+    return dx
+
+
+def conv3x3_s2_fwd(x_nhwc, w_ohwi, bias=None, stream=None):
+    """conv3x3(zero_pad(x), stride 2) + bias on the split-fp16 engine, the inference path's launch of patch embed's second convolution and of the
+    downsamplers: x (B, H, W, Ci), w (Co, 3, 3, Ci) -> (B, Ho, Wo, Co).  Ci % 4 == 0."""
+    _check_operands("conv3x3_s2_fwd", x_nhwc, w_ohwi, bias)
+    if x_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[1:]) != (3, 3, x_nhwc.shape[-1]) or x_nhwc.shape[-1] % 4:
+        raise ValueError(f"conv3x3_s2_fwd: x {tuple(x_nhwc.shape)} must be (B, H, W, Ci) with Ci % 4 == 0 and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
+    B, H, W, Ci = x_nhwc.shape
+    Co = w_ohwi.shape[0]
+    y = _f32((B, _s2_out(H), _s2_out(W), Co), x_nhwc.device)
+    wsplit = _split_h2(w_ohwi.reshape(Co, 9 * Ci), stream=stream)
+    _launch("xp_conv3x3_nhwc_h2", x_nhwc, stream, ptr(x_nhwc), ctypes.c_void_p(wsplit.data_ptr()), ptr(y), ptr(bias), None, None, B, H, W, Ci, Co, 2, 0, 0)
+    return y
+
+
+def stem_conv(img, w9co, bias, stream=None):
+    """The stem's convolution alone: img (B, 1, H, W) or (B, H, W), w9co (9, Co) the weight folded over the three identical input channels, bias
+    (Co,) -> (B, Ho, Wo, Co).  The device definition the inference path fuses with LayerNorm and GELU.  Co 48 or 16."""
+    _check_operands("stem_conv", img, w9co, bias)
+    if img.dim() == 4 and img.shape[1] == 1:
+        img = img[:, 0]
+    if img.dim() != 3 or w9co.dim() != 2 or w9co.shape[0] != 9 or tuple(bias.shape) != (w9co.shape[1],) or min(img.shape) < 1:
+        raise ValueError(f"stem_conv: img (B, 1, H, W), w9co (9, Co), bias (Co,); got {tuple(img.shape)}, {tuple(w9co.shape)}, {tuple(bias.shape)}")
+    B, H, W = img.shape
+    Co = w9co.shape[1]
+    y = _f32((B, _s2_out(H), _s2_out(W), Co), img.device)
+    _launch("xp_stem_conv", img, stream, ptr(img.contiguous()), ptr(w9co.contiguous()), ptr(bias.contiguous()), ptr(y), B, H, W, Co)
+    return y
+
+
+def stem_conv_wgrad(img, dy_nhwc, dy_scale=None, stream=None):
+    """dw9co (9, Co) of the stem's convolution: img (B, 1, H, W) or (B, H, W), dy (B, Ho, Wo, Co); dy_scale {S, 1 / S}: dy holds S x the gradient.
+    f64 accumulators in the fixed order of colsum_rows (which gives the bias gradient)."""
+    _check_operands("stem_conv_wgrad", img, dy_nhwc, dy_scale)
+    if img.dim() == 4 and img.shape[1] == 1:
+        img = img[:, 0]
+    if img.dim() != 3 or dy_nhwc.dim() != 4 or min(img.shape) < 1 or tuple(dy_nhwc.shape[:3]) != (img.shape[0], _s2_out(img.shape[1]), _s2_out(img.shape[2])):
+        raise ValueError(f"stem_conv_wgrad: dy {tuple(dy_nhwc.shape)} is not the stride-2 output grid of img {tuple(img.shape)}")
+    B, H, W = img.shape
+    Co = dy_nhwc.shape[-1]
+    dw = _f32((9, Co), img.device)
+    _launch("xp_stem_conv_wgrad", img, stream, ptr(img.contiguous()), ptr(dy_nhwc.contiguous()), ptr(dw), B, H, W, Co, _vp(dy_scale),
+            ws=_ws(img.device, "stem_conv_wgrad", Co))
+    return dw
+
+
 def bn_train_fwd(x, gamma, beta, eps=BN_EPS, y=None, stream=None):
     """x (rows, C) rows with any ld -> (y, save_mean (2, C), save_invstd, biased batch variance)."""
     _check_operands("bn_train_fwd", x, gamma, beta, y)

@@ -2,7 +2,7 @@
 section 16): LayerNorm, in_proj, depthwise conv + SiLU, x_proj, the dt projection, the SS2D core composed from the differentiable cross-scan /
 selective-scan / cross-merge operators, out_norm, out_proj and the MLP, with stochastic depth.  Its backward is HIP only and passes the gradient
 through to its input, so blocks stack.  Every linear layer takes its input gradient by `_linear_dgrad` (the forward engine on the transposed weight).
-Not built: the gradient of patch embed / downsample."""
+Patch embed, the downsamplers and the stacking of the blocks are encoder.py's (VSSEncoder)."""
 import math
 
 import torch
