@@ -156,9 +156,14 @@ __device__ __forceinline__ void dt_tile(const DtWeights<R>& w, const float* rows
     const int fr = threadIdx.x & 31, fh = (threadIdx.x >> 5) & 1;
     f32x16 acc[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 2; ++j) {
+        // (the accumulators' start value is the same for every tile; opaque here so that the two 16-register start tuples are rebuilt per tile — 32 moves —
+        //  instead of being hoisted out of the caller's tile loop and held beside the working accumulators for the whole kernel)
+        float b0 = w.bias[j];
+        if constexpr (!AMP) asm volatile("" : "+v"(b0));                // (AMP starts from the constant 0)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = w.bias[j];
+        for (int e = 0; e < 16; ++e) acc[j][e] = b0;
+    }
 #pragma unroll
     for (int ks = 0; ks < DtWeights<R>::KS; ++ks) {
         const int k0 = ks * 16 + fh * 8;
@@ -564,6 +569,13 @@ __global__ __launch_bounds__(768) void ss2d_pass3(SS2DParams p) {
 // are fetched a 32-pixel tile ahead.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int SEQ_TP = 32;
+// The dt_rank >= 16 kernels below are held to TWO waves per SIMD: vector + accumulator registers <= 256 of the SIMD's 512 per lane.  A lone wave issues a
+// vector instruction every ~5.4 cycles, two resident waves one every ~2.7 (tools/pkfma_probe.hip), and these kernels are issue-bound.  The attribute makes the
+// register allocator keep the bound; it must be met without scratch (profiles/ss2d_seq_occupancy.txt has the compiler's report).
+constexpr int SEQ_RESIDENT = 2;
+#define XP_SEQ_TWO_WAVES __attribute__((amdgpu_waves_per_eu(2)))
+typedef volatile __attribute__((address_space(3))) int* SeqLdsInt;      // the wave-to-wave turn protocol's LDS words, accessed with DS instructions
+typedef volatile __attribute__((address_space(3))) float* SeqLdsFloat;
 template <int R>
 __global__ __launch_bounds__(64) void ss2d_seq_scan(SS2DParams p, float* __restrict__ ys) {
     constexpr int RW = R + 2, HW2 = RW / 2;                             // floats / float2 pieces per xdbl row of one route
@@ -660,6 +672,21 @@ __global__ __launch_bounds__(64) void ss2d_seq_scan(SS2DParams p, float* __restr
     }
 }
 
+// Which route a workgroup of the dt_rank >= 16 kernels takes.  Workgroup ids go round-robin to the 8 XCDs, one L2 each, and the four routes of one (image,
+// 64-channel group) read the same u columns and the same xdbl rows: in grid order (channel group fastest, then route) they land on four different XCDs and u
+// is fetched past L2 four times per launch (profiles/ss2d_seq_occupancy.txt).  Here ids 8 q + x, q = 4 s .. 4 s + 3, are the four routes of group x (G / 8) + s: one
+// XCD, adjacent slots, and every XCD takes one contiguous run of groups — the channel groups of the same few images, whose xdbl rows then pass through one
+// L2 instead of eight.  Groups past the last whole eight keep a plain order.  A bijection of the grid: placement only, never results.
+__device__ __forceinline__ void seq_block_route(int& cg, int& d, int& b) {
+    const int gx = gridDim.x, G = gx * gridDim.z;
+    const int lin = blockIdx.x + gx * (blockIdx.y + 4 * blockIdx.z);
+    const int whole = (G >> 3) * 32;
+    int g;
+    if (lin < whole) { const int q = lin >> 3; d = q & 3; g = (lin & 7) * (G >> 3) + (q >> 2); }
+    else { const int rem = lin - whole; d = rem & 3; g = (G & ~7) + (rem >> 2); }
+    b = g / gx; cg = g - b * gx;
+}
+
 // Sequential form for dt_rank >= 16 (the deep stages), written for INSTRUCTION COUNT: with one wave per SIMD every instruction of any
 // kind — scalar address arithmetic, branches, LDS reads — is issue time, and the first kernel above spends ~3 500 of them per 32-pixel
 // tile (64-bit scalar address chains per access, a branchy scalar walk of the pixel order, R FMAs per step).  Here
@@ -675,16 +702,18 @@ __global__ __launch_bounds__(64) void ss2d_seq_scan(SS2DParams p, float* __restr
 //    so there is one code path for full and partial tiles;
 //  * the tile's xdbl rows are fetched one row per lane pair with immediate offsets (no address arithmetic).
 template <int R, bool AMP = false>
-__global__ __launch_bounds__(64) void ss2d_seq_scan2(SS2DParams p, float* __restrict__ ys) {
+__global__ __launch_bounds__(64) XP_SEQ_TWO_WAVES void ss2d_seq_scan2(SS2DParams p, float* __restrict__ ys) {
     constexpr int RW = R + 2, NP = RW / 2, NPL = (NP + 1) / 2;          // float2 pieces per xdbl row of one route; pieces fetched by one lane
     __shared__ __align__(16) float s_x[2][SEQ_TP * RW];
-    const int lane = threadIdx.x, d = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x;
+    int cg, d, b;
+    seq_block_route(cg, d, b);
     const int pair = d >> 1, back = d & 1;                              // directions in the stored order (0, 2, 1, 3)
     const int fr = lane & 31, fh = lane >> 5;
     const int L = p.H * p.W, XD = 4 * RW;
-    const int c = blockIdx.x * 64 + lane;                               // C % 64 == 0 (host)
+    const int c = cg * 64 + lane;                                       // C % 64 == 0 (host)
     DtWeights<R> dw;
-    dt_load_weights<R, AMP>(dw, p.wdt + (int64_t)d * R * p.C, p.dtb + d * p.C, p.C, blockIdx.x * 64);
+    dt_load_weights<R, AMP>(dw, p.wdt + (int64_t)d * R * p.C, p.dtb + d * p.C, p.C, cg * 64);
     const float Av = XP_L2E * p.A[d * p.C + c], Dv = p.Dp[d * p.C + c];
     const int plane_bytes = L * p.C * 4;                                // host: < 2^31
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(p.u + (int64_t)b * L * p.C), 0, plane_bytes, 0x00020000);
@@ -773,24 +802,26 @@ __global__ __launch_bounds__(64) void ss2d_seq_scan2(SS2DParams p, float* __rest
 // then waits for its turn (an LDS counter), takes the running state from LDS, runs the 32 chain steps + stores, and passes the state on.  The chain itself is the
 // same instruction sequence in the same order (h = a * h + b; y = C * h + D u with the same operands), so the results are bit-identical to ss2d_seq_scan2;
 // what changes is that the chain's length, not the evaluation's, sets the time.  All NW waves of a workgroup are resident together, so the turn wait cannot
-// deadlock; a waiting wave sleeps (s_sleep) on a SIMD nobody else of the workgroup uses.
+// deadlock; a waiting wave sleeps (s_sleep) on a SIMD nobody else of the workgroup uses (a wave of another workgroup may: two are resident per SIMD).
 template <int R, bool AMP, int NW>
-__global__ __launch_bounds__(64 * NW) void ss2d_seq_scan3(SS2DParams p, float* __restrict__ ys) {
+__global__ __launch_bounds__(64 * NW) XP_SEQ_TWO_WAVES void ss2d_seq_scan3(SS2DParams p, float* __restrict__ ys) {
     constexpr int RW = R + 2, NP = RW / 2, NPL = (NP + 1) / 2;
     __shared__ __align__(16) float s_x[NW][2][SEQ_TP * RW];
     __shared__ float s_h[64];
     __shared__ int s_turn;
-    const int lane = threadIdx.x & 63, d = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x & 63;
+    int cg, d, b;
+    seq_block_route(cg, d, b);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pair = d >> 1, back = d & 1;
     const int fr = lane & 31, fh = lane >> 5;
     const int L = p.H * p.W, XD = 4 * RW;
-    const int c = blockIdx.x * 64 + lane;
+    const int c = cg * 64 + lane;
     if (threadIdx.x < 64) s_h[lane] = 0.f;
     if (threadIdx.x == 0) s_turn = 0;
     __syncthreads();
     DtWeights<R> dw;
-    dt_load_weights<R, AMP>(dw, p.wdt + (int64_t)d * R * p.C, p.dtb + d * p.C, p.C, blockIdx.x * 64);
+    dt_load_weights<R, AMP>(dw, p.wdt + (int64_t)d * R * p.C, p.dtb + d * p.C, p.C, cg * 64);
     const float Av = XP_L2E * p.A[d * p.C + c], Dv = p.Dp[d * p.C + c];
     const int plane_bytes = L * p.C * 4;
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(p.u + (int64_t)b * L * p.C), 0, plane_bytes, 0x00020000);
@@ -842,38 +873,64 @@ __global__ __launch_bounds__(64 * NW) void ss2d_seq_scan3(SS2DParams p, float* _
     for (int t = wave; t < ntile; t += NW, ++it) {
         if (t + NW < ntile) { tile_offsets(t + NW, offn, offx); load_tile(offn, offx, unext); }
         const float* sx = s_x[wave][it & 1];                            // (written and read by this wave only: LDS operations of a wave execute in order)
-        float dtv[2][16];
-        dt_tile<R, AMP>(dw, sx, RW, dtv);
-        float a[SEQ_TP], bb[SEQ_TP], cv[SEQ_TP];
+        // Only what the chain needs is held across the turn: a[], bb[] and the tile's u (C stays in the wave's LDS tile, D u is formed after the turn).
+        float a[SEQ_TP], bb[SEQ_TP];
+        {
+            float dtv[2][16];
+            dt_tile<R, AMP>(dw, sx, RW, dtv);
 #pragma unroll
-        for (int j = 0; j < SEQ_TP; ++j) {
-            const float2 bc = *reinterpret_cast<const float2*>(sx + j * RW + R);
-            float delta;
-            xp_softplus_decay_l2_nb(XP_DTV(dtv, j), Av, delta, a[j]);
-            bb[j] = delta * bc.x * ucur[j];
-            cv[j] = bc.y;
-            ucur[j] = Dv * ucur[j];                                     // D u: the second product of y = C h + D u, rounded as before
+            for (int j = 0; j < SEQ_TP; ++j) {
+                float delta;
+                xp_softplus_decay_l2_nb(XP_DTV(dtv, j), Av, delta, a[j]);
+                bb[j] = delta * sx[j * RW + R] * ucur[j];
+            }
         }
         // (pin the tile's operand evaluation BEFORE the turn wait: they are pure arithmetic, which the compiler may otherwise sink past the wait, into the chain)
 #pragma unroll
-        for (int j = 0; j < SEQ_TP; ++j) asm volatile("" :: "v"(a[j]), "v"(bb[j]), "v"(cv[j]), "v"(ucur[j]));
+        for (int j = 0; j < SEQ_TP; ++j) asm volatile("" :: "v"(a[j]), "v"(bb[j]));
+        // the next tile's xdbl rows go to the tile's other LDS buffer now (they were requested before the evaluation above, and that buffer was last read
+        // before this iteration began), so that their registers are not held across the turn
+        if (t + NW < ntile) store_x((it + 1) & 1);
         // my turn: every tile before t has passed its state on
         // (LDS only, and LDS operations of a wave execute in order: plain volatile accesses + compiler barriers.  An acquire / release pair at workgroup
-        //  scope would also drain the wave's outstanding GLOBAL stores and prefetch loads — s_waitcnt vmcnt(0) — into the chain: measured 1.5x instead of 3x)
-        while (*reinterpret_cast<volatile int*>(&s_turn) != t) __builtin_amdgcn_s_sleep(1);
+        //  scope would also drain the wave's outstanding GLOBAL stores and prefetch loads — s_waitcnt vmcnt(0) — into the chain: measured 1.5x instead of 3x.
+        //  The pointers carry the LDS address space: through a generic volatile pointer each of these accesses is a FLAT instruction followed by that
+        //  same s_waitcnt vmcnt(0).)
+        SeqLdsInt turn = (SeqLdsInt)&s_turn;
+        SeqLdsFloat hst = (SeqLdsFloat)&s_h[lane];
+        while (*turn != t) __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
-        float h = *reinterpret_cast<volatile float*>(&s_h[lane]);
+        float h = *hst;
+        // the turn is the chain and nothing else: 32 dependent updates, h_j written over a[j]
 #pragma unroll
         for (int j = 0; j < SEQ_TP; ++j) {
             h = a[j] * h + bb[j];
-            const float y = cv[j] * h + ucur[j];                        // y = C*h + D*u (csms6s.py:61,67)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), ry, cbyte, __builtin_amdgcn_readlane(offc, j), 0);
+            a[j] = h;
         }
-        *reinterpret_cast<volatile float*>(&s_h[lane]) = h;
+        *hst = h;
         asm volatile("" ::: "memory");
-        *reinterpret_cast<volatile int*>(&s_turn) = t + 1;
+        *turn = t + 1;
+        asm volatile("" ::: "memory");
+        // off the turn, while the next wave runs its chain: y = C*h + D*u (csms6s.py:61,67) — C from this wave's own LDS tile (store_x above wrote the
+        // tile's OTHER buffer) into the registers bb[] has left, D u the same rounded product as before, in place — and the 32 stores with their
+        // v_readlane.  (The empty asm statements keep the products and the lane reads from being scheduled up into the turn: volatile asm statements stay
+        // in program order.  D u has a loop of its own so that the compiler's packed multiplies pair neighbouring steps, not C h with D u of one step,
+        // which needs h_j and u_j copied into a register pair.)
+        float cv[SEQ_TP];
+#pragma unroll
+        for (int j = 0; j < SEQ_TP; ++j) cv[j] = sx[j * RW + R + 1];
+        int offs = offc;
+        asm volatile("" : "+v"(offs));
+#pragma unroll
+        for (int j = 0; j < SEQ_TP; ++j) asm volatile("" : "+v"(ucur[j]));
+#pragma unroll
+        for (int j = 0; j < SEQ_TP; ++j) ucur[j] = Dv * ucur[j];
+#pragma unroll
+        for (int j = 0; j < SEQ_TP; ++j) {
+            const float y = cv[j] * a[j] + ucur[j];
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), ry, cbyte, __builtin_amdgcn_readlane(offs, j), 0);
+        }
         if (t + NW < ntile) {
-            store_x((it + 1) & 1);
 #pragma unroll
             for (int j = 0; j < SEQ_TP; ++j) ucur[j] = unext[j];
             offc = offn;
@@ -946,9 +1003,13 @@ int launch_ss2d_seq(const SS2DParams& p, float* ys, hipStream_t s, bool half_out
         const bool v2 = seq_scan2_applies(R, p.H, p.W, p.C);
         if constexpr (R >= 16 && R % 8 == 0) {
             // waves per route (ss2d_seq_scan3): XP_SS2D_SEQ_NW = 1 selects the one-wave kernel (bit-identical results)
-            // as many waves per route as the chip has idle SIMDs for: 4 while 4 x routes fit the SIMDs once, else 2, else the one-wave kernel (more waves than
-            // SIMDs only add turn waits: 16 images at C = 384: 142 / 99 / 109 us with 1 / 2 / 4; at C = 768: 54 / 62 / 66; 2 images at C = 384: 116 / 70 / 46).
-            // Bit-identical for every NW (tools/ss2d_bench.py prints the CRC), so the choice may depend on the batch.
+            // As many waves per route as can all be RESIDENT: the largest NW of 4 / 2 / 1 with routes x NW <= (resident waves per SIMD of that instance) x
+            // SIMDs.  Every dt_rank >= 16 instance fits two waves per SIMD (XP_SEQ_TWO_WAVES), so that is 2 x 1024 waves on an MI355X: NW = 4 up to 21 images
+            // at C = 384 and 10 at C = 768, NW = 2 up to 42 / 21.  Waves that are not resident run as a second round of workgroups and only add turn waits.
+            // Whole core (scan + merge), tools/ss2d_bench.py, us with NW = 1 / 2 / 4 — 16 images: C = 384 141 / 119 / 81, C = 768 54 / 49 / 50 (3072 waves: not
+            // resident); 2 images: C = 384 114 / 71 / 45, C = 768 42 / 32 / 25 (profiles/ss2d_seq_occupancy.txt; forced NW = 2 at C = 384, 16 images, was 99 when the
+            // register file kept its 768 waves one to a SIMD — where two may share one they now do; the rule never picks it there).
+            // Bit-identical for every NW (tools/ss2d_bench.py prints the CRC, tests/test_gpu_ss2d_seq_bits.py holds the digests), so the choice may depend on the batch.
             static const int force_nw = getenv("XP_SS2D_SEQ_NW") ? atoi(getenv("XP_SS2D_SEQ_NW")) : 0;
             static int n_simd = 0;
             if (n_simd == 0) {
@@ -956,9 +1017,28 @@ int launch_ss2d_seq(const SS2DParams& p, float* ys, hipStream_t s, bool half_out
                 if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
                 n_simd = 4 * v;
             }
+            // waves per SIMD that the runtime really keeps resident of each instance (NW = 1, 2, 4), asked once: registers and LDS as compiled, so a
+            // build that misses the two-wave bound sizes NW for one wave instead of queueing a second round of workgroups
+            static int resident[2][3] = {{0, 0, 0}, {0, 0, 0}};
+            auto waves_per_simd = [&](int k) {                          // k = log2(NW)
+                int& r = resident[half_out ? 1 : 0][k];
+                if (r == 0) {
+                    int nb = 0;
+                    hipError_t e;
+                    if (k == 2) e = half_out ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan3<R, true, 4>, 256, 0)
+                                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan3<R, false, 4>, 256, 0);
+                    else if (k == 1) e = half_out ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan3<R, true, 2>, 128, 0)
+                                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan3<R, false, 2>, 128, 0);
+                    else e = half_out ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan2<R, true>, 64, 0)
+                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ss2d_seq_scan2<R, false>, 64, 0);
+                    const int w = e == hipSuccess ? (nb << k) / 4 : 1;  // workgroups per CU x NW waves over the CU's 4 SIMDs
+                    r = w < 1 ? 1 : (w > SEQ_RESIDENT ? SEQ_RESIDENT : w);      // (more than two add nothing: two already fill the issue slots)
+                }
+                return r;
+            };
             const dim3 grid(xp_cdiv(p.C, 64), 4, p.Bn);
             const int64_t routes = (int64_t)grid.x * grid.y * grid.z;
-            const int nw = force_nw ? force_nw : (routes * 4 <= n_simd ? 4 : (routes * 2 <= n_simd ? 2 : 1));
+            const int nw = force_nw ? force_nw : (routes * 4 <= (int64_t)waves_per_simd(2) * n_simd ? 4 : (routes * 2 <= (int64_t)waves_per_simd(1) * n_simd ? 2 : 1));
             if (v2 && nw == 4) {
                 if (half_out) hipLaunchKernelGGL((ss2d_seq_scan3<R, true, 4>), grid, dim3(256), 0, s, p, ys);
                 else hipLaunchKernelGGL((ss2d_seq_scan3<R, false, 4>), grid, dim3(256), 0, s, p, ys);
