@@ -677,8 +677,8 @@ int xp_aug_photo_step(const float* src, float* dst, const int* ops, const float*
  * 4352 + ceil(M / XP_WGRAD_CHUNK) I J 4 bytes, 256-byte aligned.
  * xp_conv3x3_wgrad_h2: the same with Q = the im2col view of the NHWC input x (batch, H, W, Ci) under reflection padding 1, stride 1 (columns in
  * (ky, kx, ci) order), P = dy (batch H W, Co): dw (Co, 3, 3, Ci), bit-equal to xp_gemm_tn_h2 on the materialised im2col matrix.  Any other
- * stride / reflect_pad is refused.  Workspace: xp_gemm_tn_h2_workspace_bytes(batch H W, Co, 9 Ci).  No input gradient is built for the reflection-padded
- * convolution (the zero-padded one has xp_conv3x3_dgrad_h2, below). */
+ * stride / reflect_pad is refused.  Workspace: xp_gemm_tn_h2_workspace_bytes(batch H W, Co, 9 Ci).  The input gradient of the reflection-padded
+ * convolution is xp_conv3x3_rp_dgrad_h2 (the zero-padded one has xp_conv3x3_dgrad_h2), both below. */
 #define XP_WGRAD_CHUNK 256
 size_t xp_gemm_tn_h2_workspace_bytes(int M, int I, int J);
 int xp_gemm_tn_h2(const float* P, const float* Q, float* out, int M, int I, int J, int ldp, int ldq, int ldo, const float* p_scale,
@@ -722,8 +722,8 @@ int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, float* dx, int6
  *   NULL: S is taken here from the largest magnitude of dy (max|dy| S in [2^13, 2^14)) and a scaled copy in the workspace is what the engine reads,
  *   so any finite gradient range is accepted.  dx is the UNSCALED gradient (1 / S is applied, exactly, by the epilogue).  Co % 4 == 0 (the engine
  *   loads dy in 4-element channel groups); |w| is unrestricted (row scales of the offline split).  Workspace:
- *   xp_conv3x3_dgrad_h2_workspace_bytes, 256-byte aligned.  The reflection-padded convolution gets no input gradient in this build; the
- *   stride-2 one has xp_conv3x3_s2_dgrad_h2, below.
+ *   xp_conv3x3_dgrad_h2_workspace_bytes, 256-byte aligned.  The reflection-padded convolution has xp_conv3x3_rp_dgrad_h2 and the stride-2 one
+ *   xp_conv3x3_s2_dgrad_h2, both below.
  * xp_relu_fwd: y = max(x, 0) over n elements.  xp_relu_bwd: dy = dr where y > 0, else 0 (y the ReLU's input or its output).
  * xp_maxpool2_relu_bwd: backward of MaxPool2d(2) over ReLU(y), y (batch, H, W, C) the BatchNorm output, dpool (batch, H / 2, W / 2, C):
  *   dy = dpool of the window at the FIRST position, in row-major order inside the window, that attains the window's maximum, provided the maximum is
@@ -819,6 +819,25 @@ int xp_stem_conv(const float* img, const float* w9co, const float* bias, float* 
 size_t xp_stem_conv_wgrad_workspace_bytes(int Co);
 int xp_stem_conv_wgrad(const float* img, const float* dy, float* dw9co, int batch, int H, int W, int Co, const float* dy_scale, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training of the whole XPoint (xpoint_amd/training/model.py XPointNet; csrc/train_dense.hip): the input gradient of the head
+ * trunk's REFLECTION-padded 3x3 convolution (XPoint.py:112-138), which carries the heads' loss into the encoder.
+ *
+ * xp_conv3x3_rp_dgrad_h2: dx (batch, H, W, Ci) from dy (batch, H, W, Co) and w (Co, 3, 3, Ci), the contract of xp_conv3x3_dgrad_h2: dy_scale NULL
+ *   (S is taken here from max|dy|, any finite range) or a device float[2] {S, 1 / S} for a dy that already holds S x the gradient (what
+ *   xp_bn_train_bwd writes); dx is the UNSCALED gradient.  With g the zero-padded input gradient on the padded frame (rows -1 .. H, columns
+ *   -1 .. W), dx[y][x] = sum of g[v][u] over v in {y} + {-1 if y == 1} + {H if y == H - 2} and u likewise: the interior term is
+ *   xp_conv3x3_dgrad_h2's launch as it stands; the frame (2 (W + 2) + 2 H pixels per image, three taps each) is twelve thin implicit GEMMs (four
+ *   sides x three taps, K = Co each) on the split-fp16 tile engine over the slices of one rearranged weight that is split once per call; a last
+ *   kernel adds the three tap planes and the frame terms to the pixels of rows and columns 1 and n - 2 in a fixed order.  No (H + 2) x (W + 2)
+ *   copy of dy or dx, no atomics: two calls are bit-identical and a sample's dx does not depend on its batch neighbours (given dy_scale).
+ *   Co % 4 == 0, H, W >= 2 (reflection needs 2), the shape limits of xp_conv3x3_dgrad_h2 otherwise; beyond its contract: dy 16-byte aligned and
+ *   12 Ci pad32(Co) < 2^31 (the rearranged weight's elements).
+ *   Workspace: xp_conv3x3_rp_dgrad_h2_workspace_bytes, 256-byte aligned. */
+size_t xp_conv3x3_rp_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co);
+int xp_conv3x3_rp_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the

@@ -148,6 +148,7 @@ _SIGNATURES = {
     "xp_conv3x3_s2_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
     "xp_stem_conv": [c_p] * 4 + [c_i] * 4 + [c_p],
     "xp_stem_conv_wgrad": [c_p] * 3 + [c_i] * 4 + [c_p, c_p, c_sz, c_p],
+    "xp_conv3x3_rp_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -196,6 +197,7 @@ _SIZE_QUERIES = {
     "xp_dwconv3x3_silu_bwd_workspace_bytes": (c_sz, [c_i] * 4),
     "xp_conv3x3_s2_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
     "xp_stem_conv_wgrad_workspace_bytes": (c_sz, [c_i]),
+    "xp_conv3x3_rp_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
 }
 
 

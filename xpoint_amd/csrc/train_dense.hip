@@ -1,7 +1,8 @@
 // Dense backward kernels of head training: the weight-gradient GEMM on the split-fp16 matrix path, its implicit 3x3 form,
 // BatchNorm training forward / backward over NHWC rows, the column sums behind the bias gradients and the L2-normalise backward; at the end of the
 // file the zero-padded 3x3 convolution's weight gradient and INPUT gradient of the homography head, the same two for the STRIDE-2 convolutions
-// of patch embed and the downsamplers with the stem's weight gradient (encoder training), and xp_scale_grad, the amax / power-of-two
+// of patch embed and the downsamplers with the stem's weight gradient (encoder training), the INPUT gradient of the head trunk's
+// reflection-padded convolution (whole-model training), and xp_scale_grad, the amax / power-of-two
 // / scale kernels of the weight gradient as an entry point of their own (VSS-block training).  The row walks and the fixed-order column sums
 // are in train_rows.h, which train_vss.hip shares.
 //
@@ -850,6 +851,223 @@ extern "C" int xp_stem_conv_wgrad(const float* img, const float* dy, float* dw9c
     hipLaunchKernelGGL(td_stem_wgrad_parts_kernel, dim3(xp_cdiv(Co, 32), BN_PARTS), dim3(256), 0, s, img, dy, H, W, Ho, Wo, rows, Co, part);
     XP_LAUNCH_CHECK();
     hipLaunchKernelGGL(td_stem_wgrad_finish_kernel, dim3(xp_cdiv(9 * Co, 256)), dim3(256), 0, s, part, Co, (const float2*)dy_scale, dw9co);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+// ---- the REFLECTION-padded 3x3 convolution of the head trunk (XPoint.py:112-138): input gradient ----
+// With g the zero-padded input gradient on the PADDED frame (rows -1 .. H, columns -1 .. W; g[v][u] = sum_k w[k]^T dy[v - ky + 1][u - kx + 1], taps
+// outside dy absent), reflection folds the frame back: dx[y][x] = sum of g[v][u] over v in {y} + {-1 if y == 1} + {H if y == H - 2} and u likewise.
+// The interior term g[y][x] is xp_conv3x3_dgrad_h2 as it stands.  The frame — 2 (W + 2) + 2 H pixels per image — is a thin implicit GEMM of its own
+// in four classes (top row v = -1: only ky = 0, from dy row 0; bottom row v = H: only ky = 2, from dy row H - 1; left column u = -1: only kx = 0;
+// right column u = W: only kx = 2), each cut by its three taps along the line: twelve GEMMs with M = the class's frame pixels, N = Ci, K = Co over
+// their slice of ONE rearranged weight that is split once per call (every slice padded to whole 32-wide slabs), the scheme of the stride-2 input
+// gradient above.  The cut by tap keeps the reduction short — the frame has few rows, so one workgroup per (row tile, class) walking K = 3 Co alone
+// would be a long serial loop on a few CUs — and the three partial results go to three planes that the last kernel adds in tap order, together with
+// the fold: it adds the frame terms to the at most 2 (H + W) - 4 pixels of rows / columns 1 and n - 2 in a fixed order.  No (H + 2) x (W + 2) copy
+// of dy or dx, no atomics.
+namespace {
+
+static int td_rp_span(int Co) { return xp_cdiv(Co, H2_BK) * H2_BK; }          // K of one (class, tap) slice
+static int td_rp_frame(int H, int W) { return 2 * (W + 2) + 2 * H; }          // per image: top (W + 2), bottom (W + 2), left (H), right (H)
+
+// wf[ci][span (3 cls + t) + co] = w[co][ky][kx][ci]: cls 0 (ky, kx) = (0, t), 1: (2, t), 2: (t, 0), 3: (t, 2); zeros in the pad of every slice
+__global__ __launch_bounds__(256) void td_rp_weights_kernel(const float* __restrict__ w, float* __restrict__ wf, int Ci, int Co, int span) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Ci * 12 * span) return;
+    const int ci = idx / (12 * span), rem = idx - ci * 12 * span, slice = rem / span, co = rem - slice * span;
+    float v = 0.f;
+    if (co < Co) {
+        const int cls = slice / 3, t = slice - 3 * cls;
+        const int ky = cls == 0 ? 0 : (cls == 1 ? 2 : t), kx = cls == 2 ? 0 : (cls == 3 ? 2 : t);
+        v = w[((int64_t)co * 9 + ky * 3 + kx) * Ci + ci];
+    }
+    wf[idx] = v;
+}
+
+struct RpDgParams {
+    const float* dy;         // S x the gradient, (batch, H, W, Co)
+    const uint4* wsplit;     // xp_split_weights_h2 of wf (Ci, 12 span)
+    const float* wscale;     // its Ci inverse row scales
+    const float2* scale;     // {S, 1 / S}
+    float* gf;               // (3, batch, frame, Ci): the unscaled g on the frame, one plane per tap
+    float* dx;               // (batch, H, W, Ci): holds the interior term, receives the frame terms
+    int batch, H, W, Ci, Co;
+    int slabs;               // slabs per (class, tap) slice
+};
+
+// Row m of class cls is frame pixel i of sample b: i = u + 1 along the top / bottom row, i = v along the left / right column.  Tap t reads the dy
+// pixel at line position i - t (rows: the column u - kx + 1) or i - t + 1 (columns: the row v - ky + 1) of dy's first / last row or column.
+template <int TN>
+__global__ __launch_bounds__(256) void td_rp_frame_kernel(const RpDgParams p) {
+    using T = GemmTileH2<2, 2, 1, TN>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[T::kLdsBytes];
+    const int cls = blockIdx.z / 3, tap = blockIdx.z - 3 * cls;
+    const bool horiz = cls < 2;
+    const int Lc = horiz ? p.W + 2 : p.H, n_line = horiz ? p.W : p.H;
+    const int Mc = p.batch * Lc, Kc = p.Co;
+    const int m0 = blockIdx.x * T::BM, n0 = blockIdx.y * T::BN;
+    if (m0 >= Mc) return;                          // block-uniform, before any barrier: this class has fewer row tiles
+    // dy pixel of line position j: pix0 + j * step
+    const int pix0 = cls == 1 ? (p.H - 1) * p.W : (cls == 3 ? p.W - 1 : 0), step = horiz ? 1 : p.W, shift = horiz ? 0 : 1;
+
+    const float* a_ptr[T::A_LD];
+    bool a_ok[T::A_LD];
+#pragma unroll
+    for (int s = 0; s < T::A_LD; ++s) {
+        const int m = m0 + T::a_row(s);
+        const int mc = m < Mc ? m : 0;           // rows past Mc only feed output rows that are never stored
+        const int b = mc / Lc;
+        int j = mc - b * Lc + shift - tap;      // the line position this row's tap reads: fixed for the whole K loop
+        a_ok[s] = j >= 0 && j < n_line;
+        j = j < 0 ? 0 : (j < n_line ? j : n_line - 1);     // a valid address: the load is unconditional, the slot is staged as zeros
+        a_ptr[s] = p.dy + ((int64_t)b * p.H * p.W + pix0 + (int64_t)j * step) * p.Co;
+    }
+    const int nslab = (Kc + H2_BK - 1) / H2_BK;
+    const uint4* w_unit[T::B_LD];
+#pragma unroll
+    for (int s = 0; s < T::B_LD; ++s) {
+        const int n = n0 + T::b_row(s);
+        w_unit[s] = p.wsplit + (int64_t)(n < p.Ci ? n : 0) * H2_SLAB_UNITS + T::b_unit(s);
+    }
+    const int64_t w_slab = (int64_t)p.Ci * H2_SLAB_UNITS;
+    const int slab0 = (int)blockIdx.z * p.slabs;
+    auto ldA = [&](int s, int k, float4& v) -> bool {
+        const bool ok = k < Kc;                            // k is the channel: a multiple of 4, so k < Co leaves four channels
+        v = *reinterpret_cast<const float4*>(a_ptr[s] + (ok ? k : 0));
+        return ok && a_ok[s];
+    };
+    auto ldB = [&](int s, int t) -> uint4 { return w_unit[s][(slab0 + (t < nslab ? t : nslab - 1)) * w_slab]; };
+
+    f32x16 acc[1][TN];
+    T::run(lds, Kc, ldA, ldB, acc);
+
+    const float inv_s = p.scale->y;
+    const int F = 2 * (p.W + 2) + 2 * p.H;
+    const int off = cls == 0 ? 0 : (cls == 1 ? p.W + 2 : (cls == 2 ? 2 * (p.W + 2) : 2 * (p.W + 2) + p.H));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m0 + T::row_of(0, r);
+        if (m >= Mc) continue;
+        const int b = m / Lc, i = m - b * Lc;
+        float* row = p.gf + (((int64_t)tap * p.batch + b) * F + off + i) * p.Ci;
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn) {
+            const int n = n0 + T::col_of(jn);
+            if (n < p.Ci) row[n] = acc[0][jn][r] * p.wscale[n] * inv_s;
+        }
+    }
+}
+
+// dx[y][x] += the frame terms (each the sum of its three tap planes, in tap order), rows of the frame first (top, bottom: u = x, then -1, then W), then the columns (left, right) at v = y.  The pixels of
+// rows 1 and H - 2 come first (nry W of them), then those of columns 1 and W - 2 in the remaining rows.
+__global__ __launch_bounds__(256) void td_rp_fold_kernel(const RpDgParams p, int nry, int ry0, int ry1, int ncx, int cx0, int cx1, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int na = nry * p.W + (p.H - nry) * ncx;           // affected pixels per image
+    const int c = (int)(idx % p.Ci);
+    const int64_t pa = idx / p.Ci;
+    const int b = (int)(pa / na), a = (int)(pa - (int64_t)b * na);
+    int y, x;
+    if (a < nry * p.W) { const int q = a / p.W; y = q ? ry1 : ry0; x = a - q * p.W; }
+    else {
+        const int r = a - nry * p.W, q = r / ncx;
+        x = (r - q * ncx) ? cx1 : cx0;
+        y = q; if (y >= ry0) ++y; if (nry == 2 && y >= ry1) ++y;
+    }
+    const int F = 2 * (p.W + 2) + 2 * p.H;
+    const int64_t plane = (int64_t)p.batch * F * p.Ci;
+    auto term = [&](const float* q) { return (q[0] + q[plane]) + q[2 * plane]; };
+    const float* g = p.gf + (int64_t)b * F * p.Ci + c;
+    const float* top = g, *bot = g + (int64_t)(p.W + 2) * p.Ci, *lef = g + (int64_t)2 * (p.W + 2) * p.Ci, *rig = lef + (int64_t)p.H * p.Ci;
+    float* d = p.dx + (((int64_t)b * p.H + y) * p.W + x) * p.Ci + c;
+    const bool xl = x == 1, xr = x == p.W - 2;
+    float s = *d;
+    if (y == 1) {
+        s += term(top + (int64_t)(x + 1) * p.Ci);
+        if (xl) s += term(top);
+        if (xr) s += term(top + (int64_t)(p.W + 1) * p.Ci);
+    }
+    if (y == p.H - 2) {
+        s += term(bot + (int64_t)(x + 1) * p.Ci);
+        if (xl) s += term(bot);
+        if (xr) s += term(bot + (int64_t)(p.W + 1) * p.Ci);
+    }
+    if (xl) s += term(lef + (int64_t)y * p.Ci);
+    if (xr) s += term(rig + (int64_t)y * p.Ci);
+    *d = s;
+}
+
+struct RpDgradLayout { size_t wf, wsplit, gf, total; };
+static RpDgradLayout td_rp_dgrad_layout(int batch, int H, int W, int Ci, int Co) {
+    RpDgradLayout l{};
+    const int Ktot = 12 * td_rp_span(Co);
+    l.wf = td_dgrad_layout(batch, H, W, Ci, Co).total;                       // the interior launch's workspace comes first, as it is
+    l.wsplit = l.wf + td_up256((size_t)Ci * Ktot * sizeof(float));
+    l.gf = l.wsplit + td_up256(xp_split_weights_h2_bytes(Ci, Ktot));
+    l.total = l.gf + td_up256((size_t)3 * batch * td_rp_frame(H, W) * Ci * sizeof(float));
+    return l;
+}
+static bool td_rp_shape_ok(int batch, int H, int W, int Ci, int Co) {
+    // the limits of the zero-padded input gradient, reflection's two pixels, and the rearranged weight's 12 Ci pad32(Co) elements indexed as int
+    return td_conv_shape_ok(batch, H, W, Ci, Co) && H >= 2 && W >= 2 && (int64_t)12 * Ci * td_rp_span(Co) < ((int64_t)1 << 31);
+}
+
+template <int TN>
+static int td_rp_frame_launch(const RpDgParams& p, hipStream_t s) {
+    using T = GemmTileH2<2, 2, 1, TN>;
+    const int64_t m_max = (int64_t)p.batch * max(p.W + 2, p.H);
+    hipLaunchKernelGGL(td_rp_frame_kernel<TN>, dim3((unsigned)xp_cdiv(m_max, (int64_t)T::BM), xp_cdiv(p.Ci, T::BN), 12), dim3(256), 0, s, p);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t xp_conv3x3_rp_dgrad_h2_workspace_bytes(int batch, int H, int W, int Ci, int Co) {
+    if (!td_rp_shape_ok(batch, H, W, Ci, Co)) return 0;
+    return td_rp_dgrad_layout(batch, H, W, Ci, Co).total;
+}
+
+extern "C" int xp_conv3x3_rp_dgrad_h2(const float* dy, const float* w, float* dx, int batch, int H, int W, int Ci, int Co, const float* dy_scale,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    XP_CHECK_ARG(dy && w && dx, "xp_conv3x3_rp_dgrad_h2: null pointer");
+    XP_CHECK_ARG(td_rp_shape_ok(batch, H, W, Ci, Co), "xp_conv3x3_rp_dgrad_h2: bad shape batch=%d H=%d W=%d Ci=%d Co=%d (reflection needs H, W >= 2)",
+                 batch, H, W, Ci, Co);
+    XP_CHECK_ARG(Co % 4 == 0, "xp_conv3x3_rp_dgrad_h2: Co must be a multiple of 4 (got %d): the engine loads dy in 4-element channel groups", Co);
+    XP_CHECK_ARG(((uintptr_t)dy & 15) == 0, "xp_conv3x3_rp_dgrad_h2: dy must be 16-byte aligned");
+    const RpDgradLayout l = td_rp_dgrad_layout(batch, H, W, Ci, Co);
+    XP_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= l.total,
+                 "xp_conv3x3_rp_dgrad_h2: workspace of %zu bytes, 256-byte aligned, needed (got %zu)", l.total, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    // the interior term g[y][x]: the zero-padded input gradient as it stands, in the head of the workspace
+    XP_TRY(xp_conv3x3_dgrad_h2(dy, w, dx, batch, H, W, Ci, Co, dy_scale, workspace, l.wf, stream));
+    const float2* scale = (const float2*)dy_scale;
+    if (!dy_scale) {          // it left {S, 1 / S} and the scaled copy of dy in its workspace
+        scale = (const float2*)(ws + AMAX_PARTS * 4);
+        dy = (const float*)(ws + td_dgrad_layout(batch, H, W, Ci, Co).dys);
+    }
+    const int span = td_rp_span(Co), Ktot = 12 * span;
+    float* wf = (float*)(ws + l.wf);
+    hipLaunchKernelGGL(td_rp_weights_kernel, dim3(xp_cdiv(Ci * Ktot, 256)), dim3(256), 0, s, w, wf, Ci, Co, span);
+    XP_LAUNCH_CHECK();
+    XP_TRY(xp_split_weights_h2(wf, ws + l.wsplit, Ci, Ktot, stream));
+    RpDgParams p{};
+    p.dy = dy; p.wsplit = (const uint4*)(ws + l.wsplit); p.wscale = h2_scales(ws + l.wsplit, Ci, Ktot); p.scale = scale;
+    p.gf = (float*)(ws + l.gf); p.dx = dx;
+    p.batch = batch; p.H = H; p.W = W; p.Ci = Ci; p.Co = Co; p.slabs = span / H2_BK;
+    const int64_t frame_rows = (int64_t)batch * td_rp_frame(H, W);
+    {
+        XpProfScope prof("conv3x3_rp_dgrad_frame_h2", s, 6.0 * frame_rows * 3.0 * Ci * Co, 4.0 * frame_rows * (3.0 * Co + Ci));
+        XP_TRY(Ci <= 64 ? td_rp_frame_launch<1>(p, s) : td_rp_frame_launch<2>(p, s));
+    }
+    // rows {1, H - 2} and columns {1, W - 2} as sets: H = 2 gives {0, 1} (H - 2 first does not matter: the order inside a pixel's sum is fixed), H = 3 {1}
+    const int ry0 = min(1, H - 2), ry1 = max(1, H - 2), nry = ry0 == ry1 ? 1 : 2;
+    const int cx0 = min(1, W - 2), cx1 = max(1, W - 2), ncx = cx0 == cx1 ? 1 : 2;
+    const int64_t total = (int64_t)batch * (nry * W + (H - nry) * ncx) * Ci;
+    XpProfScope prof("conv3x3_rp_dgrad_fold", s, 0.0, 16.0 * total);
+    hipLaunchKernelGGL(td_rp_fold_kernel, dim3((unsigned)xp_cdiv(total, (int64_t)256)), dim3(256), 0, s, p, nry, ry0, ry1, ncx, cx0, cx1, total);
     XP_LAUNCH_CHECK();
     return XP_OK;
 }

@@ -1,16 +1,19 @@
-"""Training on the HIP library over a frozen (or partly frozen) encoder: forward and backward of three trainable modules, HIP only, no CPU fallback.
+"""Training on the HIP library, of the whole VMamba XPoint or of its parts over a frozen encoder: forward and backward of the trainable modules, HIP
+only, no CPU fallback.
 
     ops.py      the operator level: one wrapper per training kernel, the shared forward launches, the module base
     heads.py    XPointHeads, finetune_step: the detector and descriptor heads (section 14)
     regnet.py   RegNetHead: the homography regression head (section 15)
     vss.py      VSSBlock: one block of the VMamba encoder, with its input gradient (section 16)
     encoder.py  VSSEncoder: the whole VMamba encoder, patch embed and the downsamplers included (section 19)
+    model.py    XPointNet, train_step: encoder(s), heads and homography head as one model, the heads' loss reaching the encoder through the
+                input gradient of the trunk's reflection-padded convolution (section 20)
 
-Not built: the gradient of the head trunk's input (so the encoder's output gradient is not yet connected to the heads), autocast / GradScaler training,
-a training command line."""
+Not built: conv-encoder training, autocast / GradScaler training, a training command line."""
 from .encoder import VSSEncoder
 from .heads import XPointHeads, finetune_step
-from .ops import (add_scaled_rows, bn_train_bwd, bn_train_fwd, colsum_rows, conv3x3_dgrad, conv3x3_s2_dgrad, conv3x3_s2_fwd, conv3x3_s2_wgrad,
+from .model import XPointNet, train_step
+from .ops import (add_scaled_rows, bn_train_bwd, bn_train_fwd, colsum_rows, conv3x3_dgrad, conv3x3_dgrad_reflect, conv3x3_s2_dgrad, conv3x3_s2_fwd, conv3x3_s2_wgrad,
                   conv3x3_wgrad, conv3x3_wgrad_zero_pad, costvolume_mean_bwd, dropout_rows, dwconv3x3_silu_bwd, gelu_bwd, gelu_fwd, gemm_tn,
                   l2norm_rows_bwd, layernorm_bwd, maxpool2_relu_bwd, relu_bwd, scale_grad, stem_conv, stem_conv_wgrad)
 from .regnet import RegNetHead
@@ -19,4 +22,5 @@ from .vss import VSSBlock, drop_path_rates
 __all__ = ["XPointHeads", "RegNetHead", "finetune_step", "gemm_tn", "conv3x3_wgrad", "bn_train_fwd", "bn_train_bwd", "colsum_rows", "l2norm_rows_bwd",
            "conv3x3_wgrad_zero_pad", "conv3x3_dgrad", "relu_bwd", "maxpool2_relu_bwd", "costvolume_mean_bwd", "dropout_rows",
            "VSSBlock", "layernorm_bwd", "dwconv3x3_silu_bwd", "gelu_fwd", "gelu_bwd", "add_scaled_rows", "scale_grad",
-           "VSSEncoder", "conv3x3_s2_wgrad", "conv3x3_s2_dgrad", "conv3x3_s2_fwd", "stem_conv", "stem_conv_wgrad"]
+           "VSSEncoder", "conv3x3_s2_wgrad", "conv3x3_s2_dgrad", "conv3x3_s2_fwd", "stem_conv", "stem_conv_wgrad",
+           "conv3x3_dgrad_reflect", "XPointNet", "train_step"]

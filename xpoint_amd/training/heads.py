@@ -12,14 +12,15 @@ one Ci -> 512 launch of the inference path.  In `.train()` BatchNorm uses the st
 nn.BatchNorm2d does (momentum 0.1, eps 1e-5, unbiased variance for the running value); in `.eval()` it uses the running statistics and the
 forward is the inference path's launches.  The backward is three `torch.autograd.Function`s whose dense arithmetic is HIP only: weight
 gradients by xp_conv3x3_wgrad_h2 / xp_gemm_tn_h2, BatchNorm by xp_bn_train_bwd, bias gradients by xp_colsum_rows, the 1x1 layers' input
-gradient by xp_gemm_nt_h2 on the transposed weight, F.normalize by xp_l2norm_rows_bwd.  Torch only concatenates / permutes parameters and
-gradients.  There is no CPU fallback and no gradient for the encoder: an `enc_nhwc` that requires grad raises NotImplementedError.
+gradient by xp_gemm_nt_h2 on the transposed weight, F.normalize by xp_l2norm_rows_bwd, the trunk's input gradient by xp_conv3x3_rp_dgrad_h2.  Torch
+only concatenates / permutes parameters and gradients.  There is no CPU fallback.  The public `forward` is the frozen-encoder path: an `enc_nhwc` that
+requires grad raises NotImplementedError; training.XPointNet (model.py) is what passes the heads' gradient on to the encoder.
 Activations must stay below 65504 in magnitude (the encoder output and the trunk's BatchNorm output: O(1) in this network)."""
 import torch
 
 from .. import _lib
 from .ops import (BN_EPS, TrainModule, _conv3x3_h2, _gemm_nt_h2, _l2norm_rows, _L2NormFn, _linear, _linear_dgrad, _need_device, _pad4, _split_h2, bn_train_bwd,
-                  bn_train_fwd, colsum_rows, conv3x3_wgrad, gemm_tn)
+                  bn_train_fwd, colsum_rows, conv3x3_dgrad_reflect, conv3x3_wgrad, gemm_tn)
 
 _DET, _DSC = "detector_head_convolutions.", "descriptor_head_convolutions."
 
@@ -32,15 +33,16 @@ class _TrunkFn(torch.autograd.Function):
         B, H, W, _ = enc.shape
         Co = w.shape[0]
         st = _lib.current_stream(enc)            # looked up once per call: every launch below goes to it
-        a = _conv3x3_h2(enc, w.contiguous(), b.contiguous(), stream=st)
+        w = w.contiguous()
+        a = _conv3x3_h2(enc, w, b.contiguous(), stream=st)
         h, mean, invstd, var = bn_train_fwd(a.view(B * H * W, Co), gamma.contiguous(), beta.contiguous(), stream=st)
-        ctx.save_for_backward(enc, a, gamma, mean, invstd)
+        ctx.save_for_backward(enc, a, gamma, mean, invstd, w)
         ctx.mark_non_differentiable(mean, var)
         return h.view(B, H, W, Co), mean, var
 
     @staticmethod
     def backward(ctx, dh, _dm, _dv):
-        enc, a, gamma, mean, invstd = ctx.saved_tensors
+        enc, a, gamma, mean, invstd, w = ctx.saved_tensors
         B, H, W, Co = a.shape
         dh = dh.contiguous().view(B * H * W, Co)
         # the trunk's order is conv -> ReLU -> BatchNorm: the masked, scaled dx is the gradient of the convolution's output
@@ -48,7 +50,8 @@ class _TrunkFn(torch.autograd.Function):
         da, dgamma, dbeta, scale = bn_train_bwd(dh, a.view(B * H * W, Co), gamma.contiguous(), mean, invstd, relu_mask=True, scaled=True, stream=st)
         db = colsum_rows(da, scale, stream=st)
         dw = conv3x3_wgrad(enc, da.view(B, H, W, Co), scale, stream=st)
-        return None, dw, db, dgamma, dbeta
+        denc = conv3x3_dgrad_reflect(da.view(B, H, W, Co), w, scale, stream=st) if ctx.needs_input_grad[0] else None
+        return denc, dw, db, dgamma, dbeta
 
 
 class _TailFn(torch.autograd.Function):
@@ -128,12 +131,16 @@ class XPointHeads(TrainModule):
         """enc_nhwc (B, Hc, Wc, Ci) on the GPU -> {'logits': (B, 65, Hc, Wc), 'desc': (B, D, Hc, Wc)} (channel-last memory, NCHW shape)."""
         _need_device(enc_nhwc, "XPointHeads")
         if enc_nhwc.requires_grad:
-            raise NotImplementedError("XPointHeads: the encoder is frozen in this build (no convolution input gradient); pass a detached enc_nhwc")
+            raise NotImplementedError("XPointHeads: the encoder is frozen on this path (training.XPointNet trains it); pass a detached enc_nhwc")
         if enc_nhwc.dim() != 4 or enc_nhwc.shape[-1] != self.in_channels:
             raise ValueError(f"XPointHeads: enc_nhwc must be (B, Hc, Wc, {self.in_channels}), got {tuple(enc_nhwc.shape)}")
         if self.t(_DET + "1.weight").device != enc_nhwc.device:
             raise _lib.XPointHipError("XPointHeads: parameters and enc_nhwc live on different devices")
-        enc = enc_nhwc.detach().to(torch.float32).contiguous()
+        return self._forward(enc_nhwc.detach())
+
+    def _forward(self, enc_nhwc):
+        """forward's body on the tensor as it is: an enc_nhwc that requires grad receives the trunk's input gradient (training.XPointNet's path)."""
+        enc = enc_nhwc.to(torch.float32).contiguous()
         B, Hc, Wc, _ = enc.shape
         rows, Ch = B * Hc * Wc, self.head_channels
         cat = lambda suffix: torch.cat([self.t(_DET + suffix), self.t(_DSC + suffix)], 0)

@@ -123,6 +123,21 @@ def conv3x3_dgrad(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
     return dx
 
 
+def conv3x3_dgrad_reflect(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
+    """Input gradient (B, H, W, Ci) of the stride-1 REFLECTION-padded 3x3 convolution (the head trunk's) from dy (B, H, W, Co) and w (Co, 3, 3, Ci):
+    conv3x3_dgrad's launch plus the frame terms that reflection folds back onto rows and columns 1 and n - 2.  dy_scale as conv3x3_dgrad's; the
+    result is the unscaled gradient either way.  Co % 4 == 0; H, W >= 2."""
+    _check_operands("conv3x3_dgrad_reflect", dy_nhwc, w_ohwi, dy_scale)
+    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3):
+        raise ValueError(f"conv3x3_dgrad_reflect: dy {tuple(dy_nhwc.shape)} must be (B, H, W, Co) and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
+    B, H, W, Co = dy_nhwc.shape
+    Ci = w_ohwi.shape[-1]
+    dx = _f32((B, H, W, Ci), dy_nhwc.device)
+    ws = _ws(dy_nhwc.device, "conv3x3_rp_dgrad_h2", B, H, W, Ci, Co)
+    _launch("xp_conv3x3_rp_dgrad_h2", dy_nhwc, stream, ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
+    return dx
+
+
 def _s2_out(n):
     """Output length of the 3x3 stride-2 padding-1 convolution along an axis of n pixels."""
     return (n - 1) // 2 + 1
