@@ -840,6 +840,37 @@ int xp_conv3x3_rp_dgrad_h2(const float* dy, const float* w, float* dx, int batch
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The optimiser step (xpoint_amd/training/optim.py Adam; csrc/optim.hip): the global gradient norm, a device record that
+ * decides whether the step is applied, and torch.optim.Adam's update (L2 weight decay, amsgrad off) in f32 over every tensor.  The pointer and count
+ * arrays are HOST arrays of n_tensors entries; they travel to the device BY VALUE in the kernel arguments, 64 tensors per launch, so the caller may
+ * reuse them as soon as the call returns.  No atomics, no host read-back, no allocation: the three calls of a step may be captured.
+ *
+ * xp_optim_grad_sumsq: every workgroup writes ONE f64 partial sum of g^2 over its 8192 elements of one tensor into workspace[slot], the slot fixed
+ *   by (tensor index, offset); *n_partials (host) receives the number of slots = sum_j ceil(counts[j] / 8192).  16-byte loads where a gradient's
+ *   address allows, 4-byte ones where not (a lane owns the same elements either way).  Workspace: xp_optim_workspace_bytes(n_tensors, sum of
+ *   counts) (an upper bound), 8-byte aligned.
+ * xp_optim_step_header: one workgroup adds the partials in a fixed order and writes the record at `header` (xp_optim_header_bytes() = 64 bytes,
+ *   8-byte aligned, zeroed by the caller before the first step), eight 8-byte words:
+ *     f64 norm2 | f64 bc1 = 1 - beta1^t | f64 bc2 = 1 - beta2^t | f64 clip_coef | i64 t | i64 skipped | i64 finite | i64 applied
+ *   finite = norm2 is finite (an inf or NaN in any gradient makes it not: the whole detection); applied = finite or !skip_nonfinite; t advances
+ *   only when applied, else `skipped` does; clip_coef = min(1, max_norm / (sqrt(norm2) + 1e-6)), or 1 when max_norm <= 0 (clipping off).
+ * xp_optim_adam_apply: reads the record; applied == 0: writes NOTHING.  Else per element, in f32 with no contraction:
+ *     g' = clip_coef g + wd p;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ *   m, v at exp_avg / exp_avg_sq + moment_offsets[j] (flat buffers of moment_elements floats, 16-byte aligned; [offset, offset + count) must lie
+ *   inside).  16-byte accesses per array where its address allows, 4-byte ones where not: any 4-byte aligned pointer and any offset are handled,
+ *   and an element's result does not depend on its tensor's alignment or place in the table.
+ * Null pointers, non-positive counts and a short workspace return an error. */
+size_t xp_optim_header_bytes(void);
+size_t xp_optim_workspace_bytes(int n_tensors, int64_t total_elements);
+int xp_optim_grad_sumsq(const float* const* grads, const int64_t* counts, int n_tensors, void* workspace, size_t workspace_bytes, int64_t* n_partials,
+                        void* stream);
+int xp_optim_step_header(const void* workspace, int64_t n_partials, void* header, double beta1, double beta2, double max_norm, int skip_nonfinite,
+                         void* stream);
+int xp_optim_adam_apply(float* const* params, const float* const* grads, const int64_t* moment_offsets, const int64_t* counts, int n_tensors,
+                        float* exp_avg, float* exp_avg_sq, int64_t moment_elements, const void* header, double lr, double weight_decay, double beta1,
+                        double beta2, double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -15,6 +15,7 @@ c_p = ctypes.c_void_p
 c_i = ctypes.c_int
 c_f = ctypes.c_float
 c_l = ctypes.c_int64
+c_d = ctypes.c_double
 
 
 class XPointHipError(RuntimeError):
@@ -149,6 +150,9 @@ _SIGNATURES = {
     "xp_stem_conv": [c_p] * 4 + [c_i] * 4 + [c_p],
     "xp_stem_conv_wgrad": [c_p] * 3 + [c_i] * 4 + [c_p, c_p, c_sz, c_p],
     "xp_conv3x3_rp_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
+    "xp_optim_grad_sumsq": [c_p, c_p, c_i, c_p, c_sz, ctypes.POINTER(c_l), c_p],
+    "xp_optim_step_header": [c_p, c_l, c_p, c_d, c_d, c_d, c_i, c_p],
+    "xp_optim_adam_apply": [c_p] * 4 + [c_i, c_p, c_p, c_l, c_p] + [c_d] * 5 + [c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],
@@ -198,6 +202,8 @@ _SIZE_QUERIES = {
     "xp_conv3x3_s2_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
     "xp_stem_conv_wgrad_workspace_bytes": (c_sz, [c_i]),
     "xp_conv3x3_rp_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
+    "xp_optim_header_bytes": (c_sz, []),
+    "xp_optim_workspace_bytes": (c_sz, [c_i, c_l]),
 }
 
 

@@ -325,7 +325,7 @@ def hm_regression_points(optical_H, thermal_H, h, w, patch=128):
     return np.subtract(np.array(pert), np.array(four)).astype(np.int64), (min(ys), max(ys), min(xs), max(xs))
 
 
-def augment_pair_batch(batch, config, rng, seed, labels_follow_warp=True, homographies=None, warp_optical=None):
+def augment_pair_batch(batch, config, rng, seed, labels_follow_warp=True, homographies=None, warp_optical=None, hm_input=True):
     """ImagePairDataset.__getitem__ :349-430 for the batched device dict `batch` of `ImagePairDataset.load_batch`; config = the
     reference's config['augmentation'] ({'photometric': {...}, 'homographic': {...}}).  Photometric runs on both images when enabled
     (one call over the 2B images; sample ids 0 .. B-1 optical, B .. 2B-1 thermal), then homographic: one coin per sample decides which
@@ -336,6 +336,7 @@ def augment_pair_batch(batch, config, rng, seed, labels_follow_warp=True, homogr
     Returns {'optical': {'image' (B,1,h,w) f32, 'keypoints' (B,h,w) bool (when the batch has labels), 'valid_mask' (B,1,h,w) bool,
     'homography' (B,3,3) f32 (identity on the unwarped side), 'is_optical'}, 'thermal': {...}, 'name'} and, with homographic.enable,
     'hm_input' (B,2,128,128) f32 and 'hfour_points' (B,4,2) int64 (prep_hm_regression_input, quirks kept: see hm_regression_points).
+    hm_input=False (a model without the homography head) leaves these two out, and with them the demand that the 128 x 128 crop fits.
 
     labels_follow_warp=True labels the warped image with the warped points (geometrically consistent); False reproduces the reference,
     whose pair branch discards the warped points and labels the warped image with the unwarped ones (:407-415)."""
@@ -353,7 +354,7 @@ def augment_pair_batch(batch, config, rng, seed, labels_follow_warp=True, homogr
     out = {'optical': {}, 'thermal': {}}
     kp = {'optical': opt.get('keypoints'), 'thermal': th.get('keypoints')}
     if hcfg.get('enable', False):
-        if h // 2 < 64 or w // 2 < 64 or h // 2 + 64 > w or w // 2 + 64 > h:      # the corner (h // 2 - 64, w // 2 - 64) is used as (x, y)
+        if hm_input and (h // 2 < 64 or w // 2 < 64 or h // 2 + 64 > w or w // 2 + 64 > h):      # the corner (h // 2 - 64, w // 2 - 64) is used as (x, y)
             raise ValueError(f"augment_pair_batch: the 128 x 128 homography-head crop does not fit a {h} x {w} image")
         params = hcfg.get('params', {})
         corner = params.get('corner_homography', {})
@@ -382,11 +383,12 @@ def augment_pair_batch(batch, config, rng, seed, labels_follow_warp=True, homogr
         if kmaps is not None:
             maps = kw_maps if labels_follow_warp else kmaps
             out['optical']['keypoints'], out['thermal']['keypoints'] = maps[:B], maps[B:]
-        pts = np.zeros((B, 4, 2), np.int64)
-        for i in range(B):
-            pts[i], (y0, y1, x0, x1) = hm_regression_points(Ho[i], Ht[i], h, w)
-        out['hm_input'] = torch.cat([img_o[:, :, y0:y1, x0:x1], img_t[:, :, y0:y1, x0:x1]], 1).contiguous()
-        out['hfour_points'] = _dev(pts, dev)
+        if hm_input:
+            pts = np.zeros((B, 4, 2), np.int64)
+            for i in range(B):
+                pts[i], (y0, y1, x0, x1) = hm_regression_points(Ho[i], Ht[i], h, w)
+            out['hm_input'] = torch.cat([img_o[:, :, y0:y1, x0:x1], img_t[:, :, y0:y1, x0:x1]], 1).contiguous()
+            out['hfour_points'] = _dev(pts, dev)
     else:
         for key, src in (('optical', opt), ('thermal', th)):
             out[key]['valid_mask'] = torch.ones((B, 1, h, w), dtype=torch.bool, device=dev)

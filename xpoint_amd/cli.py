@@ -1,10 +1,16 @@
-"""Thin command-line front ends of the two prediction flows, with the reference scripts' arguments
-(predict_align_image_pair.py:24-37, predict_keypoints.py: the same -y / -m / -v / -i / -s options):
+"""Thin command-line front ends of the two prediction flows, the label export and the training run, with the reference scripts' arguments
+(predict_align_image_pair.py:24-37, predict_keypoints.py: the same -y / -m / -v / -i / -s options; train.py: -y / -w):
 
     python -m xpoint_amd.cli align     -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e] [-o out.npz]
     python -m xpoint_amd.cli keypoints -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e [-t 3]] [-o out.npz]
     python -m xpoint_amd.cli export    -y configs/config_export_keypoints.yaml -m model_weights/XPoint-EXP1 -v latest -o labels.npz
                                        [-i 0] [-n all] [-s 0] [--chunk K]
+    python -m xpoint_amd.cli train     -y configs/cmt.yaml [-w <output_directory>/e20.model] [-s 0]
+
+`train` is train.py (xpoint_amd.training.fit, whose docstring lists what is kept and what differs): the VMamba XPoint on pairs of a folder dataset
+with keypoint labels, Adam with weight decay and a device-side guard against non-finite gradients, the LR schedule, validation, `params.yaml`,
+`e<N>.model` / `latest.model` (and `e<N>.optim`, from which -w e<N>.model resumes the optimiser) in training.output_directory.  It reads everything
+from the YAML; -m, -v, -i, -n are not used.
 
 What is kept from the scripts: the YAML handling (model params from <model-dir>/params.yaml overwrite config['model'], the
 `use_attention` height / width patch of predict_align_image_pair.py:50-54), `<model-dir>/<version>.model` loaded with
@@ -125,7 +131,7 @@ def evaluate_keypoints(args, config, dataset, net) -> dict:
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m xpoint_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('flow', choices=['align', 'keypoints', 'export'])
+    ap.add_argument('flow', choices=['align', 'keypoints', 'export', 'train'])
     ap.add_argument('-y', '--yaml-config', default='configs/cipdp.yaml', help='YAML config file')
     ap.add_argument('-m', '--model-dir', default='model_weights/xpoint', help='Directory of the model')
     ap.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
@@ -139,10 +145,13 @@ def main(argv=None):
     ap.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
     ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz')
     ap.add_argument('--chunk', default=None, type=int, help='export: homographies per forward (does not change the result)')
+    ap.add_argument('-w', '--weight-file', default=None, help='train: file containing the weights to initialize the weights (e<N>.model resumes at epoch N)')
     ap.add_argument('--device', default='cuda:0')
     args = ap.parse_args(argv)
     if args.flow == 'export':
         return export(args)
+    if args.flow == 'train':
+        return train(args)
     if args.count is None:
         args.count = 1
 
@@ -193,6 +202,16 @@ def main(argv=None):
     if args.output:
         np.savez(args.output, **out)
     return out
+
+
+def train(args):
+    """train.py (see the module docstring): xpoint_amd.training.fit on the YAML config."""
+    with open(args.yaml_config, 'r') as f:
+        config = yaml.load(f, Loader=yaml.FullLoader)
+    if not torch.cuda.is_available():
+        raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
+    from . import training
+    return training.fit(config, weight_file=args.weight_file, device=args.device, seed=args.seed)
 
 
 def export(args):

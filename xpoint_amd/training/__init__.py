@@ -8,14 +8,19 @@ only, no CPU fallback.
     encoder.py  VSSEncoder: the whole VMamba encoder, patch embed and the downsamplers included (section 19)
     model.py    XPointNet, train_step: encoder(s), heads and homography head as one model, the heads' loss reaching the encoder through the
                 input gradient of the trunk's reflection-padded convolution (section 20)
+    optim.py    Adam: the optimiser step as three kinds of launch, with a global-norm clip and a device-side guard against non-finite gradients
+                (section 21)
+    fit.py      fit: the training run of the reference's train.py (epochs, augmentation, schedule, validation, checkpoints); `cli train`
 
-Not built: conv-encoder training, autocast / GradScaler training, a training command line."""
+Not built: conv-encoder training, autocast / GradScaler training."""
 from .encoder import VSSEncoder
+from .fit import fit
 from .heads import XPointHeads, finetune_step
 from .model import XPointNet, train_step
 from .ops import (add_scaled_rows, bn_train_bwd, bn_train_fwd, colsum_rows, conv3x3_dgrad, conv3x3_dgrad_reflect, conv3x3_s2_dgrad, conv3x3_s2_fwd, conv3x3_s2_wgrad,
                   conv3x3_wgrad, conv3x3_wgrad_zero_pad, costvolume_mean_bwd, dropout_rows, dwconv3x3_silu_bwd, gelu_bwd, gelu_fwd, gemm_tn,
                   l2norm_rows_bwd, layernorm_bwd, maxpool2_relu_bwd, relu_bwd, scale_grad, stem_conv, stem_conv_wgrad)
+from .optim import Adam
 from .regnet import RegNetHead
 from .vss import VSSBlock, drop_path_rates
 
@@ -23,4 +28,4 @@ __all__ = ["XPointHeads", "RegNetHead", "finetune_step", "gemm_tn", "conv3x3_wgr
            "conv3x3_wgrad_zero_pad", "conv3x3_dgrad", "relu_bwd", "maxpool2_relu_bwd", "costvolume_mean_bwd", "dropout_rows",
            "VSSBlock", "layernorm_bwd", "dwconv3x3_silu_bwd", "gelu_fwd", "gelu_bwd", "add_scaled_rows", "scale_grad",
            "VSSEncoder", "conv3x3_s2_wgrad", "conv3x3_s2_dgrad", "conv3x3_s2_fwd", "stem_conv", "stem_conv_wgrad",
-           "conv3x3_dgrad_reflect", "XPointNet", "train_step"]
+           "conv3x3_dgrad_reflect", "XPointNet", "train_step", "Adam", "fit"]

@@ -3,7 +3,7 @@ encoder(s), the detector / descriptor heads and, where the configuration has one
 (DESIGN.md section 20).
 
     model = training.XPointNet.from_model(net).cuda().train()
-    optimizer = torch.optim.Adam(model.parameters(), lr=1e-4)
+    optimizer = training.Adam(model.parameters(), lr=1e-4)          # or torch.optim.Adam; training.fit is the whole run
     loss, components = training.train_step(model, data, losses.XPointLoss(cfg), optimizer, seed=step)
     net.load_state_dict(model.state_dict(), strict=False)        # the inference model with everything tuned
 
@@ -19,6 +19,8 @@ from .ops import TrainModule, _need_device
 from .regnet import RegNetHead
 
 _HEADS = ("detector_head_convolutions", "descriptor_head_convolutions")
+MIXED_PRECISION_REFUSAL = ("XPointNet: config['mixed_precision'] = True is not built (no autocast / GradScaler training): the training kernels are the "
+                           "f32-grade class only")
 
 
 class XPointNet(TrainModule):
@@ -56,18 +58,22 @@ class XPointNet(TrainModule):
             part.training = bool(mode)          # the parts' children are this module's children: super() has set them
         return self
 
-    @classmethod
-    def from_model(cls, net):
-        """The trainable copy of a loaded models.XPoint: VMamba encoder, takes_pair.  A conv encoder or `mixed_precision: true` is refused."""
-        cfg = net.config
+    @staticmethod
+    def check_config(cfg):
+        """Refuses a model configuration (the merged `net.config`) that XPointNet does not train: a conv encoder, `mixed_precision: true`, no pairs."""
         ua = cfg['use_attention']
         if not (ua['check'] and ua['type'] == 'VMamba'):
             raise NotImplementedError("XPointNet: config['use_attention'] must select the VMamba encoder (conv-encoder training is not built)")
         if cfg['mixed_precision']:
-            raise NotImplementedError("XPointNet: config['mixed_precision'] = True is not built (no autocast / GradScaler training): the training "
-                                      "kernels are the f32-grade class only")
+            raise NotImplementedError(MIXED_PRECISION_REFUSAL)
         if not cfg['takes_pair']:
             raise NotImplementedError("XPointNet: config['takes_pair'] must be True (the losses need both spectra)")
+
+    @classmethod
+    def from_model(cls, net):
+        """The trainable copy of a loaded models.XPoint: VMamba encoder, takes_pair.  A conv encoder or `mixed_precision: true` is refused."""
+        cfg = net.config
+        cls.check_config(cfg)
         prefixes = ["encoder_thermal.", "encoder_optical."] if cfg['multispectral'] else ["encoder."]
         regnet = None
         if cfg['homography_regression_head']['check']:
