@@ -709,7 +709,7 @@ int xp_colsum_rows(const float* x, int ldx, int64_t rows, int C, const float* x_
 int xp_l2norm_rows_bwd(const float* x, int ldx, const float* dy, float* dx, int64_t rows, int C, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Training of the homography head (xpoint_amd/training.py RegNetHead; csrc/train_dense.hip, csrc/train_regnet.hip; reference
+ * Training of the homography head (xpoint_amd/training.py RegNetHead; csrc/train_dense.hip (weight gradient), csrc/train_dgrad.hip (input gradient), csrc/train_regnet.hip; reference
  * xpoint/models/RegNet.py:12-42 in training mode).  The head's layers are conv3x3 (ZERO padding 1, stride 1, no bias) -> BatchNorm -> ReLU, so the
  * ReLU gates below read the BatchNorm output and xp_bn_train_bwd runs with relu_mask = 0.
  *
@@ -748,7 +748,7 @@ int xp_dropout_rows(const float* x, float* y, unsigned char* mask /* u8, in or o
                     int tag, float p, int rows, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Training of a VSS encoder block (xpoint_amd/training.py VSSBlock; csrc/train_vss.hip, xp_scale_grad in csrc/train_dense.hip; DESIGN.md section 16;
+ * Training of a VSS encoder block (xpoint_amd/training.py VSSBlock; csrc/train_vss.hip, xp_scale_grad in csrc/train_dense.hip behind csrc/train_scale.h; DESIGN.md section 16;
  * reference VMamba.py:1153-1234 with the SS2D of forwardv2 / forward_corev2).  The block's dense layers run on xp_gemm_nt_h2 / xp_gemm_tn_h2 /
  * xp_colsum_rows and its SS2D core on xp_cross_scan / xp_selective_scan_fwd_x / xp_selective_scan_bwd_typed / xp_cross_merge; the entries below are
  * the HBM-bound rest.  All tensors are contiguous f32 rows; no atomics: every cross-row sum runs in a fixed order with f64 accumulators (the
@@ -785,7 +785,7 @@ int xp_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, float* dx
 int xp_add_scaled_rows(const float* x, const float* r, const float* s, float* y, int batch, int64_t rows_per_sample, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Training of the whole VMamba encoder (xpoint_amd/training/encoder.py VSSEncoder; csrc/train_dense.hip, csrc/elementwise.hip; DESIGN.md section 19;
+ * Training of the whole VMamba encoder (xpoint_amd/training/encoder.py VSSEncoder; csrc/train_dense.hip (weight gradients), csrc/train_dgrad.hip (input gradient), csrc/elementwise.hip; DESIGN.md section 19;
  * reference VMamba.py:1405-1440 patch embed and downsample v3, :1507-1525 VSSM.forward): the strided layers between the VSS blocks.  The convolution
  * is 3x3, ZERO padding 1, STRIDE 2: x (batch, H, W, Ci), y / dy (batch, Ho, Wo, Co) with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, w (Co, 3, 3, Ci).
  *
@@ -821,7 +821,7 @@ int xp_stem_conv_wgrad(const float* img, const float* dy, float* dw9co, int batc
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Training of the whole XPoint (xpoint_amd/training/model.py XPointNet; csrc/train_dense.hip): the input gradient of the head
+ * Training of the whole XPoint (xpoint_amd/training/model.py XPointNet; csrc/train_dgrad.hip): the input gradient of the head
  * trunk's REFLECTION-padded 3x3 convolution (XPoint.py:112-138), which carries the heads' loss into the encoder.
  *
  * xp_conv3x3_rp_dgrad_h2: dx (batch, H, W, Ci) from dy (batch, H, W, Co) and w (Co, 3, 3, Ci), the contract of xp_conv3x3_dgrad_h2: dy_scale NULL

@@ -1,4 +1,4 @@
-"""GPU: training of the homography head on the HIP library (xpoint_amd.training.RegNetHead, csrc/train_dense.hip, csrc/train_regnet.hip, DESIGN.md
+"""GPU: training of the homography head on the HIP library (xpoint_amd.training.RegNetHead, csrc/train_dense.hip, csrc/train_dgrad.hip, csrc/train_regnet.hip, DESIGN.md
 section 15) — the new operators one by one, the head end to end against the float64 restatement of tests/regnet_f64.py and the real reference's results
 (tests/golden/g31_regnet_training.npz), and a short fine-tuning run.  Bar: max |got - ref| <= 1e-4 x the scale of each tensor (the project's f32 bar);
 every comparison prints err / scale.  Gates, masks, repeatability and the eval path are compared exactly.

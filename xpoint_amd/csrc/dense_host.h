@@ -6,8 +6,6 @@
 
 #include "gemm_epilogue.h"
 
-#define XP_TRY(call) do { const int rc__ = (call); if (rc__ != XP_OK) return rc__; } while (0)
-
 // ---- tile ladder ---------------------------------------------------------------------------------------------------------------------------------------
 // The branches every engine takes from N alone: 0 = 128 x 32, 1 = 128 x 64, 2 = 128 x 96 (N = 65..96, and N = 192: two full 96-wide tiles instead of
 // 128 + 64), -1 = the engine's own M-dependent branch.

@@ -80,11 +80,8 @@ __global__ __launch_bounds__(256) void dl_amax_kernel(const float* __restrict__ 
     const float* p2 = d2 + (size_t)b * n;
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)DL_PARTS * 256) m = fmaxf(m, fmaxf(fabsf(p1[i]), fabsf(p2[i])));
-    m = xp_wave_max(m);
-    __shared__ float sm[4];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[b * DL_PARTS + blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    m = xp_block_max256(m);
+    if (threadIdx.x == 0) part[b * DL_PARTS + blockIdx.x] = m;
 }
 
 // ---- pass 0b: the sample's power of two ----

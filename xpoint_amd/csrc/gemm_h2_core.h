@@ -336,3 +336,20 @@ struct GemmTileH2R {
     }
     __device__ static __forceinline__ int col_of(int j) { return j * 32 + (int)(threadIdx.x & 31); }
 };
+
+// The B operand of both engines, ldB(slot, slab): the offline-split (N, K) weight read over the K-slice of `nslab` slabs that starts at slab `slab0` (the
+// whole matrix: slab0 = 0).  A row past N reads row 0 (its columns are never stored), a slab past the slice its last slab (the engine loads ahead).
+template <class T>
+struct H2WeightSlice {
+    const uint4* unit[T::B_LD];
+    int64_t slab;                        // 16-byte units per slab of the whole weight matrix
+    int slab0, nslab;
+    __device__ __forceinline__ H2WeightSlice(const void* wsplit, int N, int n0, int slab0_, int nslab_) : slab((int64_t)N * H2_SLAB_UNITS), slab0(slab0_), nslab(nslab_) {
+#pragma unroll
+        for (int s = 0; s < T::B_LD; ++s) {
+            const int n = n0 + T::b_row(s);
+            unit[s] = reinterpret_cast<const uint4*>(wsplit) + (int64_t)(n < N ? n : 0) * H2_SLAB_UNITS + T::b_unit(s);
+        }
+    }
+    __device__ __forceinline__ uint4 operator()(int s, int t) const { return unit[s][(slab0 + (t < nslab ? t : nslab - 1)) * slab]; }
+};

@@ -1,6 +1,6 @@
 // Element-wise and per-sample kernels of the homography head's training (reference xpoint/models/RegNet.py; xpoint_amd/training.py RegNetHead;
 // DESIGN.md §15).  The head's order is conv -> BatchNorm -> ReLU, so the ReLU gates read the BatchNorm OUTPUT (the heads' trunk is conv -> ReLU ->
-// BatchNorm and gates inside xp_bn_train_bwd).  The dense work — both zero-padded convolutions' weight and input gradients — is in train_dense.hip.
+// BatchNorm and gates inside xp_bn_train_bwd).  The dense work — both zero-padded convolutions' weight and input gradients — is in train_dense.hip and train_dgrad.hip.
 //
 //   xp_relu_fwd / xp_relu_bwd   y = max(x, 0);  dy = dr where y > 0, else 0.
 //   xp_maxpool2_relu_bwd        backward of MaxPool2d(2)(ReLU(y)) as torch computes it: the gradient of a window goes to the FIRST position (row-major

@@ -11,16 +11,12 @@
 // dx_scale follows xp_bn_train_bwd: a device float[2] that receives {S, 1 / S}, dx is written as S x the gradient (xp_scale_grad, train_dense.hip).
 // Nothing here uses an atomic: every cross-row sum runs in a fixed order with f64 accumulators, two calls are bit-identical.
 #include "train_rows.h"
+#include "train_scale.h"
 #include "xpoint_hip.h"
-
-#ifndef XP_TRY
-#define XP_TRY(call) do { const int rc__ = (call); if (rc__ != XP_OK) return rc__; } while (0)
-#endif
 
 namespace {
 
-constexpr size_t VS_HEAD_BYTES = 4352;          // xp_scale_grad's workspace, at the head of every workspace here
-static size_t vs_up256(size_t n) { return (n + 255) & ~(size_t)255; }
+// xp_scale_grad's workspace (XP_SCALE_HEAD_BYTES, train_scale.h) is at the head of every workspace here
 
 __device__ __forceinline__ double vs_group_sum(double v, int lpr) {
     for (int o = lpr / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -246,11 +242,11 @@ static int vs_elem_blocks(int64_t n) { return (int)min((int64_t)8192, max((int64
 
 static size_t vs_ln_bytes(int64_t rows, int C) {
     if (rows <= 0 || C <= 0) return 0;
-    return VS_HEAD_BYTES + vs_up256((size_t)BN_PARTS * 2 * C * sizeof(double)) + vs_up256((size_t)rows * sizeof(float2));
+    return XP_SCALE_HEAD_BYTES + xp_up256((size_t)BN_PARTS * 2 * C * sizeof(double)) + xp_up256((size_t)rows * sizeof(float2));
 }
 static size_t vs_dw_bytes(int batch, int H, int W, int C) {
     if (batch <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-    return VS_HEAD_BYTES + vs_up256((size_t)BN_PARTS * 9 * C * sizeof(double)) + vs_up256((size_t)batch * H * W * C * sizeof(float));
+    return XP_SCALE_HEAD_BYTES + xp_up256((size_t)BN_PARTS * 9 * C * sizeof(double)) + xp_up256((size_t)batch * H * W * C * sizeof(float));
 }
 
 }  // namespace
@@ -267,8 +263,8 @@ extern "C" int xp_layernorm_bwd(const float* dy, const float* x, const float* ga
                  "xp_layernorm_bwd: workspace of %zu bytes, 256-byte aligned, needed (got %zu)", vs_ln_bytes(rows, C), workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double* part = (double*)(ws + VS_HEAD_BYTES);
-    float2* stat = (float2*)(ws + VS_HEAD_BYTES + vs_up256((size_t)BN_PARTS * 2 * C * sizeof(double)));
+    double* part = (double*)(ws + XP_SCALE_HEAD_BYTES);
+    float2* stat = (float2*)(ws + XP_SCALE_HEAD_BYTES + xp_up256((size_t)BN_PARTS * 2 * C * sizeof(double)));
     const int C4 = C / 4;
     {
         XpProfScope prof("layernorm_bwd", s, 0.0, 12.0 * rows * C);
@@ -292,7 +288,7 @@ extern "C" int xp_layernorm_bwd(const float* dy, const float* x, const float* ga
         hipLaunchKernelGGL(vs_ln_param_finish_kernel, dim3(xp_cdiv(C, 256)), dim3(256), 0, s, part, C, dgamma, dbeta);
         XP_LAUNCH_CHECK();
     }
-    if (dx_scale) XP_TRY(xp_scale_grad(dx, dx, rows * C, dx_scale, workspace, VS_HEAD_BYTES, stream));
+    if (dx_scale) XP_TRY(xp_scale_grad(dx, dx, rows * C, dx_scale, workspace, XP_SCALE_HEAD_BYTES, stream));
     return XP_OK;
 }
 
@@ -308,8 +304,8 @@ extern "C" int xp_dwconv3x3_silu_bwd(const float* x, const float* w9c, const flo
                  "xp_dwconv3x3_silu_bwd: workspace of %zu bytes, 256-byte aligned, needed (got %zu)", vs_dw_bytes(batch, H, W, C), workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double* part = (double*)(ws + VS_HEAD_BYTES);
-    float* dz = (float*)(ws + VS_HEAD_BYTES + vs_up256((size_t)BN_PARTS * 9 * C * sizeof(double)));
+    double* part = (double*)(ws + XP_SCALE_HEAD_BYTES);
+    float* dz = (float*)(ws + XP_SCALE_HEAD_BYTES + xp_up256((size_t)BN_PARTS * 9 * C * sizeof(double)));
     const int64_t rows = (int64_t)batch * H * W, total = rows * (C / 4);
     {
         XpProfScope prof("dwconv3x3_silu_bwd", s, 42.0 * rows * C, 20.0 * rows * C);
@@ -325,7 +321,7 @@ extern "C" int xp_dwconv3x3_silu_bwd(const float* x, const float* w9c, const flo
         hipLaunchKernelGGL(vs_dw_dw_finish_kernel, dim3(xp_cdiv(9 * C, 256)), dim3(256), 0, s, part, C, dw9c);
         XP_LAUNCH_CHECK();
     }
-    if (dx_scale) XP_TRY(xp_scale_grad(dx, dx, rows * C, dx_scale, workspace, VS_HEAD_BYTES, stream));
+    if (dx_scale) XP_TRY(xp_scale_grad(dx, dx, rows * C, dx_scale, workspace, XP_SCALE_HEAD_BYTES, stream));
     return XP_OK;
 }
 
@@ -340,7 +336,7 @@ extern "C" int xp_gelu_fwd(const float* x, float* y, int64_t n, void* stream) {
 
 extern "C" int xp_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, float* dx_scale, void* workspace, size_t workspace_bytes, void* stream) {
     XP_CHECK_ARG(dy && x && dx && n > 0, "xp_gelu_bwd: null pointer or n <= 0");
-    XP_CHECK_ARG(!dx_scale || (workspace && workspace_bytes >= VS_HEAD_BYTES), "xp_gelu_bwd: dx_scale needs a workspace of %zu bytes", VS_HEAD_BYTES);
+    XP_CHECK_ARG(!dx_scale || (workspace && workspace_bytes >= XP_SCALE_HEAD_BYTES), "xp_gelu_bwd: dx_scale needs a workspace of %zu bytes", XP_SCALE_HEAD_BYTES);
     hipStream_t s = (hipStream_t)stream;
     {
         XpProfScope prof("gelu_bwd", s, 40.0 * n, 12.0 * n);

@@ -45,6 +45,12 @@ void xp_set_error(const char* fmt, ...);
         }                                                                                  \
     } while (0)
 
+// propagate a failed internal call (its message is already recorded)
+#define XP_TRY(call) do { const int rc__ = (call); if (rc__ != XP_OK) return rc__; } while (0)
+
+// workspace regions start on 256-byte steps
+static inline size_t xp_up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
 // Optional HIP-event timing of one launch (see api.cpp); a no-op unless xp_prof_enable(1).
 // flops / bytes are the ALGORITHMIC work of the launch (roofline numerators).
 class XpProfScope {
@@ -221,5 +227,15 @@ __device__ __forceinline__ float xp_wave_sum(float v) {        // every lane get
 __device__ __forceinline__ float xp_wave_max(float v) {
     v = xp_row16_max(v);
     return fmaxf(fmaxf(xp_lane(v, 0), xp_lane(v, 16)), fmaxf(xp_lane(v, 32), xp_lane(v, 48)));
+}
+// maximum over a block of 256 threads (wave maxima through four LDS slots), for thread 0: the others get their wave's maximum back.  Every thread must
+// call it, once per kernel
+__device__ __forceinline__ float xp_block_max256(float v) {
+    __shared__ float sm[4];
+    v = xp_wave_max(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) v = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    return v;
 }
 #endif

@@ -1,5 +1,5 @@
 """Head fine-tuning over a frozen encoder: the detector and descriptor heads of the reference's XPoint (XPoint.py:112-138, 348-371) in
-training mode, forward and backward on the HIP library (csrc/train_dense.hip).
+training mode, forward and backward on the HIP library (csrc/train_dense.hip, the trunk's input gradient in csrc/train_dgrad.hip; DESIGN.md sections 14, 20).
 
     heads = training.XPointHeads.from_model(net).cuda().train()
     optimizer = torch.optim.Adam(heads.parameters(), lr=1e-3)

@@ -1,4 +1,4 @@
-"""The operator level of xpoint_amd.training: one wrapper per training kernel of the HIP library (csrc/train_dense.hip, csrc/train_regnet.hip,
+"""The operator level of xpoint_amd.training: one wrapper per training kernel of the HIP library (csrc/train_dense.hip, csrc/train_dgrad.hip, csrc/train_regnet.hip,
 csrc/train_vss.hip), the forward launches the autograd functions share, and the base of the three trainable modules.  There is no CPU fallback.
 
 The public wrappers (`gemm_tn` ... `scale_grad`, re-exported by the package) check every operand — float32, on the GPU, one device — allocate outputs and
@@ -86,15 +86,19 @@ def gemm_tn(P, Q, out=None, p_scale=None, stream=None):
     return out
 
 
-def _conv3x3_wgrad(who, kernel, pad_args, x, dy, dy_scale, stream):
-    """The two 3x3 weight gradients differ in the entry point and in the padding arguments it takes."""
+def _conv3x3_wgrad(who, kernel, pad_args, x, dy, dy_scale, stream, stride=1):
+    """The three 3x3 weight gradients differ in the entry point, in the padding arguments it takes and in dy's grid: the input's, or its stride-2
+    output grid."""
     _check_operands(who, x, dy, dy_scale)
-    if x.dim() != 4 or dy.dim() != 4 or tuple(dy.shape[:3]) != tuple(x.shape[:3]):
-        raise ValueError(f"{who}: x {tuple(x.shape)} and dy {tuple(dy.shape)} do not share (B, H, W)")
+    if stride == 1:
+        if x.dim() != 4 or dy.dim() != 4 or tuple(dy.shape[:3]) != tuple(x.shape[:3]):
+            raise ValueError(f"{who}: x {tuple(x.shape)} and dy {tuple(dy.shape)} do not share (B, H, W)")
+    elif x.dim() != 4 or dy.dim() != 4 or min(x.shape) < 1 or tuple(dy.shape[:3]) != (x.shape[0], _s2_out(x.shape[1]), _s2_out(x.shape[2])):
+        raise ValueError(f"{who}: dy {tuple(dy.shape)} is not the stride-2 output grid of x {tuple(x.shape)}")
     B, H, W, Ci = x.shape
     Co = dy.shape[-1]
     dw = _f32((Co, 3, 3, Ci), x.device)
-    ws = _ws(x.device, "gemm_tn_h2", B * H * W, Co, 9 * Ci)
+    ws = _ws(x.device, "gemm_tn_h2", dy.shape[0] * dy.shape[1] * dy.shape[2], Co, 9 * Ci)
     _launch(kernel, x, stream, ptr(x), ptr(dy), ptr(dw), B, H, W, Ci, Co, *pad_args, _vp(dy_scale), ws=ws)
     return dw
 
@@ -109,33 +113,36 @@ def conv3x3_wgrad_zero_pad(x_nhwc, dy_nhwc, dy_scale=None, stream=None):
     return _conv3x3_wgrad("conv3x3_wgrad_zero_pad", "xp_conv3x3_zp_wgrad_h2", (), x_nhwc, dy_nhwc, dy_scale, stream)
 
 
+def _conv3x3_dgrad(who, kernel, query, dy, w, in_hw, dy_scale, stream):
+    """The three 3x3 input gradients differ in the entry point, its workspace query and in whether dy's grid is the input's (in_hw None) or its
+    stride-2 output grid."""
+    _check_operands(who, dy, w, dy_scale)
+    ok = dy.dim() == 4 and w.dim() == 4 and tuple(w.shape[:3]) == (dy.shape[-1], 3, 3)
+    if in_hw is None:
+        if not ok:
+            raise ValueError(f"{who}: dy {tuple(dy.shape)} must be (B, H, W, Co) and w {tuple(w.shape)} (Co, 3, 3, Ci)")
+        H, W = dy.shape[1:3]
+    else:
+        H, W = (int(v) for v in in_hw)
+        if not ok or H < 1 or W < 1 or tuple(dy.shape[1:3]) != (_s2_out(H), _s2_out(W)):
+            raise ValueError(f"{who}: dy {tuple(dy.shape)} must be (B, Ho, Wo, Co) of in_hw {(H, W)} and w {tuple(w.shape)} (Co, 3, 3, Ci)")
+    B, Co, Ci = dy.shape[0], dy.shape[-1], w.shape[-1]
+    dx = _f32((B, H, W, Ci), dy.device)
+    _launch(kernel, dy, stream, ptr(dy), ptr(w), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=_ws(dy.device, query, B, H, W, Ci, Co))
+    return dx
+
+
 def conv3x3_dgrad(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
     """Input gradient (B, H, W, Ci) of the stride-1 zero-padded 3x3 convolution from dy (B, H, W, Co) and w (Co, 3, 3, Ci).  dy_scale: None, or
     the device float[2] {S, 1 / S} of a dy that already holds S x the gradient; the result is the unscaled gradient either way.  Co % 4 == 0."""
-    _check_operands("conv3x3_dgrad", dy_nhwc, w_ohwi, dy_scale)
-    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3):
-        raise ValueError(f"conv3x3_dgrad: dy {tuple(dy_nhwc.shape)} must be (B, H, W, Co) and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
-    B, H, W, Co = dy_nhwc.shape
-    Ci = w_ohwi.shape[-1]
-    dx = _f32((B, H, W, Ci), dy_nhwc.device)
-    ws = _ws(dy_nhwc.device, "conv3x3_dgrad_h2", B, H, W, Ci, Co)
-    _launch("xp_conv3x3_dgrad_h2", dy_nhwc, stream, ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
-    return dx
+    return _conv3x3_dgrad("conv3x3_dgrad", "xp_conv3x3_dgrad_h2", "conv3x3_dgrad_h2", dy_nhwc, w_ohwi, None, dy_scale, stream)
 
 
 def conv3x3_dgrad_reflect(dy_nhwc, w_ohwi, dy_scale=None, stream=None):
     """Input gradient (B, H, W, Ci) of the stride-1 REFLECTION-padded 3x3 convolution (the head trunk's) from dy (B, H, W, Co) and w (Co, 3, 3, Ci):
     conv3x3_dgrad's launch plus the frame terms that reflection folds back onto rows and columns 1 and n - 2.  dy_scale as conv3x3_dgrad's; the
     result is the unscaled gradient either way.  Co % 4 == 0; H, W >= 2."""
-    _check_operands("conv3x3_dgrad_reflect", dy_nhwc, w_ohwi, dy_scale)
-    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3):
-        raise ValueError(f"conv3x3_dgrad_reflect: dy {tuple(dy_nhwc.shape)} must be (B, H, W, Co) and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
-    B, H, W, Co = dy_nhwc.shape
-    Ci = w_ohwi.shape[-1]
-    dx = _f32((B, H, W, Ci), dy_nhwc.device)
-    ws = _ws(dy_nhwc.device, "conv3x3_rp_dgrad_h2", B, H, W, Ci, Co)
-    _launch("xp_conv3x3_rp_dgrad_h2", dy_nhwc, stream, ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
-    return dx
+    return _conv3x3_dgrad("conv3x3_dgrad_reflect", "xp_conv3x3_rp_dgrad_h2", "conv3x3_rp_dgrad_h2", dy_nhwc, w_ohwi, None, dy_scale, stream)
 
 
 def _s2_out(n):
@@ -146,33 +153,14 @@ def _s2_out(n):
 def conv3x3_s2_wgrad(x_nhwc, dy_nhwc, dy_scale=None, stream=None):
     """Weight gradient (Co, 3, 3, Ci) of the zero-padded STRIDE-2 3x3 convolution (patch embed, the downsamplers): x (B, H, W, Ci),
     dy (B, Ho, Wo, Co) with Ho = (H - 1) // 2 + 1, Wo = (W - 1) // 2 + 1, contiguous.  dy_scale as gemm_tn's p_scale."""
-    _check_operands("conv3x3_s2_wgrad", x_nhwc, dy_nhwc, dy_scale)
-    if x_nhwc.dim() != 4 or dy_nhwc.dim() != 4 or min(x_nhwc.shape) < 1 or \
-            tuple(dy_nhwc.shape[:3]) != (x_nhwc.shape[0], _s2_out(x_nhwc.shape[1]), _s2_out(x_nhwc.shape[2])):
-        raise ValueError(f"conv3x3_s2_wgrad: dy {tuple(dy_nhwc.shape)} is not the stride-2 output grid of x {tuple(x_nhwc.shape)}")
-    B, H, W, Ci = x_nhwc.shape
-    Ho, Wo, Co = dy_nhwc.shape[1:]
-    dw = _f32((Co, 3, 3, Ci), x_nhwc.device)
-    ws = _ws(x_nhwc.device, "gemm_tn_h2", B * Ho * Wo, Co, 9 * Ci)
-    _launch("xp_conv3x3_s2_wgrad_h2", x_nhwc, stream, ptr(x_nhwc), ptr(dy_nhwc), ptr(dw), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
-    return dw
+    return _conv3x3_wgrad("conv3x3_s2_wgrad", "xp_conv3x3_s2_wgrad_h2", (), x_nhwc, dy_nhwc, dy_scale, stream, stride=2)
 
 
 def conv3x3_s2_dgrad(dy_nhwc, w_ohwi, in_hw, dy_scale=None, stream=None):
     """Input gradient (B, H, W, Ci) of the zero-padded STRIDE-2 3x3 convolution from dy (B, Ho, Wo, Co) and w (Co, 3, 3, Ci); in_hw = (H, W) of the
     input (Ho does not determine H).  dy_scale: None, or the device float[2] {S, 1 / S} of a dy that already holds S x the gradient; the result is the
     unscaled gradient either way.  Co % 4 == 0."""
-    _check_operands("conv3x3_s2_dgrad", dy_nhwc, w_ohwi, dy_scale)
-    H, W = (int(v) for v in in_hw)
-    if dy_nhwc.dim() != 4 or w_ohwi.dim() != 4 or tuple(w_ohwi.shape[:3]) != (dy_nhwc.shape[-1], 3, 3) or H < 1 or W < 1 or \
-            tuple(dy_nhwc.shape[1:3]) != (_s2_out(H), _s2_out(W)):
-        raise ValueError(f"conv3x3_s2_dgrad: dy {tuple(dy_nhwc.shape)} must be (B, Ho, Wo, Co) of in_hw {(H, W)} and w {tuple(w_ohwi.shape)} (Co, 3, 3, Ci)")
-    B, _, _, Co = dy_nhwc.shape
-    Ci = w_ohwi.shape[-1]
-    dx = _f32((B, H, W, Ci), dy_nhwc.device)
-    ws = _ws(dy_nhwc.device, "conv3x3_s2_dgrad_h2", B, H, W, Ci, Co)
-    _launch("xp_conv3x3_s2_dgrad_h2", dy_nhwc, stream, ptr(dy_nhwc), ptr(w_ohwi), ptr(dx), B, H, W, Ci, Co, _vp(dy_scale), ws=ws)
-    return dx
+    return _conv3x3_dgrad("conv3x3_s2_dgrad", "xp_conv3x3_s2_dgrad_h2", "conv3x3_s2_dgrad_h2", dy_nhwc, w_ohwi, in_hw, dy_scale, stream)
 
 
 def conv3x3_s2_fwd(x_nhwc, w_ohwi, bias=None, stream=None):

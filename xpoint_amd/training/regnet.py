@@ -1,5 +1,5 @@
 """The homography regression head (reference xpoint/models/RegNet.py) in training mode behind the same frozen encoder as the heads
-(csrc/train_dense.hip, csrc/train_regnet.hip): two zero-padded 3x3 convolutions in the order conv -> BatchNorm -> ReLU, max
+(csrc/train_dense.hip, csrc/train_dgrad.hip, csrc/train_regnet.hip): two zero-padded 3x3 convolutions in the order conv -> BatchNorm -> ReLU, max
 pool, F.normalize, the cost volume's global mean, and two linear layers with dropout.  Next to the heads' operators its backward uses the zero-padded
 convolution's weight gradient (xp_conv3x3_zp_wgrad_h2) and INPUT gradient (xp_conv3x3_dgrad_h2: the forward engine on the rotated, transposed
 weight), the ReLU / max-pool gates on the BatchNorm output, the cost volume's backward and a counter-based dropout.  The two linear layers take their
