@@ -43,7 +43,7 @@ def _stats(mine, ref):
 # ------------------------------------------------------------------------------------------------------------------------------ SS2D core
 def _takes_seq(H, W, C, R):
     """ss2d_takes_seq (csrc/ss2d.hip) for the fp16-storage class given f32 copies: C <= 768 and a multiple of 64, a dt_rank with whole 8-value fragment
-    halves >= 16 (seq_scan2_applies), planes inside the 32-bit buffer offsets, L <= 8192."""
+    halves >= 16 (ss2d_seq_scan2_applies), planes inside the 32-bit buffer offsets, L <= 8192."""
     return C <= 768 and C % 64 == 0 and R in (16, 24, 48) and H * W * C < 2 ** 29 and H * W * 4 * (R + 2) < 2 ** 29 and H * W <= SEQ_MAX_L
 
 

@@ -1180,7 +1180,7 @@ def test_mixed_precision_ops_vs_reference_taps(gpu_lib, golden, capsys):
 
 def test_mixed_precision_ops_vs_reference_taps_f16(gpu_lib, golden, capsys):
     """The op-by-op pin of test_mixed_precision_ops_vs_reference_taps for the HALF-STORAGE kernels of the fast class (gemm_mode "amp16f": csrc/gemm_f16.hip,
-    elementwise_f16.hip, the fp16 instances of ss2d.hip): every kernel is fed the reference's input tap AS fp16 and must reproduce the reference's output tap
+    elementwise_f16.hip, the fp16 instances of ss2d_chunked.hip / ss2d_seq.hip): every kernel is fed the reference's input tap AS fp16 and must reproduce the reference's output tap
     (g20: the real reference under float16 autocast) — >= 99 % of the elements bit-equal, the rest within 2 fp16 ulps."""
     import ctypes
     from xpoint_amd import _lib as L

@@ -1,5 +1,5 @@
 """The chunked SS2D core's pass 3 at the smallest shapes where its once-per-chunk operand loads and its after-the-loop stores can go wrong
-(csrc/ss2d.hip: a thread loads its chunk's T values of u, and the column pair the row pair's partial sums, in one batch before the forward route;
+(csrc/ss2d_chunked.hip: a thread loads its chunk's T values of u, and the column pair the row pair's partial sums, in one batch before the forward route;
 the row pair stores its T sums after the backward route).  All three instantiations of the template: f32 (xp_ss2d_core_fwd), the mixed-precision
 recipe in f32 containers (xp_set_amp_mode(1) + xp_ss2d_core_fwd) and fp16 storage (xp_ss2d_core_fwd_f16).
 

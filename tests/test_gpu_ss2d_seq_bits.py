@@ -1,4 +1,4 @@
-"""The sequential SS2D core (ss2d_seq_scan2 / ss2d_seq_scan3 + ss2d_seq_merge_ln, csrc/ss2d.hip) held to the bits of the commit BEFORE its kernels were refit
+"""The sequential SS2D core (ss2d_seq_scan2 / ss2d_seq_scan3 + ss2d_seq_merge_ln, csrc/ss2d_seq.hip) held to the bits of the commit BEFORE its kernels were refit
 to two waves per SIMD: sha256 digests of every image's output, recorded once from that commit's library by
 tools/make_golden_ss2d_seq_bits.py into tests/golden/ss2d_seq_parent_bits.json.
 

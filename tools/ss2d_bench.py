@@ -1,5 +1,5 @@
 """Micro-benchmark of xp_ss2d_core_fwd at the model's four stage shapes (16 images of 480x640).  usage: ss2d_bench.py [mode ...]
-mode: -1 auto (default), 0 chunked three-pass form, 1 sequential form.  Environment knobs (XP_SS2D_SEQ_MFMA, XP_SS2D_TBUDGET ...) are
+mode: -1 auto (default), 0 chunked three-pass form, 1 sequential form.  Environment knobs (XP_SS2D_SEQ_NW, XP_SS2D_TBUDGET ...) are
 read once per process: run one process per setting."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

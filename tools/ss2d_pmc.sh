@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes on the fused SS2D core microbench (tools/ss2d_bench.py, both precision classes): where do the wave cycles of ss2d_pass1 / pass3 / seq_scan go?
+# PMC passes on the fused SS2D core microbench (tools/ss2d_bench.py, both precision classes): where do the wave cycles of ss2d_pass1 / pass3 (csrc/ss2d_chunked.hip) / seq_scan (csrc/ss2d_seq.hip) go?
 # (the VALU-bound claim was resting on a round-1 file.)   usage on the GPU box: bash tools/ss2d_pmc.sh
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/ss2d_pmc; rm -rf $OUT; mkdir -p $OUT

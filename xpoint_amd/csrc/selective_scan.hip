@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void selective_scan_fwd_n1v2_kernel(
     const float Dval = Dv ? Dv[d] : 0.f, bias = delta_bias ? delta_bias[dd] : 0.f, An = A[d];
     float h = 0.f, pr = 1.f;
     // one step's (a, b): delta = softplus(x) (torch threshold 20), a = exp(delta * A); below the threshold both from ONE logarithm:
-    // delta = ln(1 + e^x), a = (1 + e^x)^A = 2^(A log2(1 + e^x))   (same arithmetic as step_vals in ss2d.hip)
+    // delta = ln(1 + e^x), a = (1 + e^x)^A = 2^(A log2(1 + e^x))   (same arithmetic as step_vals in ss2d_core.h)
     auto step = [&](float x, float Bu, float& a, float& bb) {
         float dl;
         if (softplus) xp_softplus_decay(x, An, dl, a);

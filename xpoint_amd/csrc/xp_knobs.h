@@ -34,8 +34,8 @@ static const XpKnob kXpKnobs[] = {
     // ---- scans
     {"XP_SS2D_SEQ", "ss2d.hip", "0 / 1: force the chunked / sequential form of the fused SS2D core (also xp_ss2d_core_set_mode)"},
     {"XP_SS2D_SEQ_MAXL", "ss2d.hip", "L bound of the automatic choice of the sequential form (default 8192)"},
-    {"XP_SS2D_SEQ_V1", "ss2d.hip", "1: first sequential kernel (dt projection on the vector ALU)"},
-    {"XP_SS2D_SEQ_NW", "ss2d.hip", "waves per route of the pipelined sequential kernel: 1 | 2 | 4"},
+    {"XP_SS2D_SEQ_V1", "ss2d_seq.hip", "1: first sequential kernel (dt projection on the vector ALU)"},
+    {"XP_SS2D_SEQ_NW", "ss2d_seq.hip", "waves per route of the pipelined sequential kernel: 1 | 2 | 4"},
     {"XP_SS2D_TBUDGET", "ss2d.hip", "chunk-length budget of the chunked passes (default 6144 pixel-channels)"},
     {"XP_SS2D_T", "ss2d.hip", "chunk length (8, 16 or 32) per channel count, e.g. \"96:32,192:16,384:16\""},
     {"XP_SS2D_THREADS", "ss2d.hip", "threads per workgroup of the chunked passes (default 192)"},
