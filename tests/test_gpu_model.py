@@ -287,19 +287,21 @@ def test_config4_1024_topk_4096_pipeline(gpu_lib):
     assert [(m.queryIdx, m.trainIdx) for m in oms] == list(zip(out["match_q"].tolist(), out["match_t"].tolist()))
 
 
-@pytest.mark.parametrize("overlap,split", [(False, 0), (True, 0), (True, 2), (True, -1)])
+@pytest.mark.parametrize("overlap,split", [(False, 0), (True, 0), (True, 2), (True, -1), (True, -3)])
 def test_hipgraph_replay_equals_eager(gpu_lib, overlap, split):
     """BASELINE configs[4] asks for a hipGraph-captured forward: a captured PairPipeline step replays to the same results as the eager
     step, with new inputs at every replay — on one stream, and for the overlapped pipeline (per output buffer one graph per encoder
-    image group + one for detection / matching, chained by events: the cross-step overlap survives capture)."""
+    image group + one for detection / matching, chained by events: the cross-step overlap survives capture).  split = -1 / -3: whole-batch
+    encoders alternating between two / rotating over three streams; five different inputs, so buffer set 0 is reused while sets 1 and 2 are in flight."""
     from xpoint_amd.predict import PairPipeline
     H, W, B = 96, 128, 2
     net = _net(synth.xpoint_exp1_config(H, W))
-    seq = [_data(s, B, H, W) for s in (0, 9, 4, 7)]
+    seq = [_data(s, B, H, W) for s in (0, 9, 4, 7, 2)]
     with torch.no_grad():
         eager = PairPipeline(net, B, H, W, cap=2048)
         refs = [eager.run(d["optical"]["image"], d["thermal"]["image"], d["optical"]["valid_mask"], d["thermal"]["valid_mask"]).fetch() for d in seq]
-        pipe = PairPipeline(net, B, H, W, cap=2048, overlap=overlap, split_encoder=max(split, 0), alternate_encoders=split < 0)   # -1: alternating encoder streams
+        pipe = PairPipeline(net, B, H, W, cap=2048, overlap=overlap, split_encoder=max(split, 0), alternate_encoders={-1: True, -3: 3}.get(split, False))
+        assert pipe.depth == {-3: 3, 0: 2 if overlap else 1}.get(split, 2)
         d0 = seq[0]
         replay = pipe.capture(d0["optical"]["image"], d0["thermal"]["image"], d0["optical"]["valid_mask"], d0["thermal"]["valid_mask"])
         for d, ref in zip(seq[1:], refs[1:]):
@@ -316,25 +318,27 @@ def test_hipgraph_replay_equals_eager(gpu_lib, overlap, split):
             assert torch.equal(a["kp_thermal"], b["kp_thermal"]) and a["match_t"].tolist() == b["match_t"].tolist()
 
 
-@pytest.mark.parametrize("split", [0, 2, 4, -1])
+@pytest.mark.parametrize("split", [0, 2, 4, -1, -3])
 def test_overlapped_pipeline_equals_single_stream(gpu_lib, split):
     """overlap=True (two streams, encoder of call i+1 behind the detection / matching of call i, double-buffered encoder
     outputs) returns exactly the single-stream results: a sequence of calls with different inputs, the caller reusing
     its input tensors right after run() returns, masks included; also with the encoder split into image groups on
-    several streams, or (split = -1) with the whole-batch encoders of consecutive calls alternating between two streams."""
+    several streams, or with the whole-batch encoders of consecutive calls alternating between two streams (split = -1) or rotating over three
+    (split = -3: with five calls back to back, buffer set 0 is reused while sets 1 and 2 are in flight)."""
     from xpoint_amd.predict import PairPipeline
     H, W, B = 96, 128, 2
     net = _net(synth.xpoint_exp1_config(H, W))
-    seq = [_data(s, B, H, W) for s in (0, 5, 9, 3)]
+    seq = [_data(s, B, H, W) for s in (0, 5, 9, 3, 7)]
     with torch.no_grad():
         single = PairPipeline(net, B, H, W, cap=2048)
         refs = []
         for d in seq:
             refs.append(single.run(d["optical"]["image"], d["thermal"]["image"], d["optical"]["valid_mask"], d["thermal"]["valid_mask"]).fetch())
-        pipe = PairPipeline(net, B, H, W, cap=2048, overlap=True, split_encoder=max(split, 0), alternate_encoders=split < 0)
+        pipe = PairPipeline(net, B, H, W, cap=2048, overlap=True, split_encoder=max(split, 0), alternate_encoders={-1: True, -3: 3}.get(split, False))
+        assert pipe.depth == (3 if split == -3 else 2)
         io, it = torch.empty_like(seq[0]["optical"]["image"]), torch.empty_like(seq[0]["thermal"]["image"])
         mo, mt = torch.empty_like(seq[0]["optical"]["valid_mask"]), torch.empty_like(seq[0]["thermal"]["valid_mask"])
-        for n_calls in (1, 2, 3, 4):
+        for n_calls in (1, 2, 3, 4, 5):
             for d in seq[:n_calls]:          # back-to-back calls, inputs refilled in place without synchronising
                 io.copy_(d["optical"]["image"]); it.copy_(d["thermal"]["image"])
                 mo.copy_(d["optical"]["valid_mask"]); mt.copy_(d["thermal"]["valid_mask"])
@@ -344,6 +348,31 @@ def test_overlapped_pipeline_equals_single_stream(gpu_lib, split):
                 assert torch.equal(a["kp_optical"], b["kp_optical"]) and torch.equal(a["kp_thermal"], b["kp_thermal"])
                 assert torch.equal(a["desc_optical"], b["desc_optical"]) and torch.equal(a["desc_thermal"], b["desc_thermal"])
                 assert a["match_q"].tolist() == b["match_q"].tolist() and a["match_t"].tolist() == b["match_t"].tolist()
+
+
+@pytest.mark.parametrize("captured", [False, True])
+def test_split_schedule_records_its_engine(gpu_lib, captured):
+    """Every step of the split-encoder schedule, eager or replayed, records the dense engine its forwards were enqueued with (PairPipeline._note_engine):
+    a range-guard trip is judged against THAT engine (_settle_engine).  Eager: "h2" (the default model) and pending from run() until the next
+    synchronisation point has read the status word — at every step, not only the first (whose allocating whole-batch forward records it too).
+    Captured: the engine the graphs were captured on."""
+    from xpoint_amd.predict import PairPipeline
+    H, W, B = 64, 96, 1
+    net = _net(synth.xpoint_exp1_config(H, W))
+    d = _data(5, B, H, W)
+    args = (d["optical"]["image"], d["thermal"]["image"], d["optical"]["valid_mask"], d["thermal"]["valid_mask"])
+    with torch.no_grad():
+        pipe = PairPipeline(net, B, H, W, cap=4096, overlap=True, split_encoder=2)
+        assert pipe.split_encoder == 2 and net.effective_gemm_mode() == "h2"
+        step = pipe.capture(*args) if captured else pipe.run
+        if captured:
+            assert pipe._graph_engine == "h2"
+        for _ in range(3):                                      # (the third step finds both buffer sets allocated)
+            step(*args)
+            assert pipe._engine_enqueued == "h2" and pipe._h2_pending                    # after the step, before any synchronisation
+            assert not captured or pipe._engine_enqueued == pipe._graph_engine
+            pipe.fetch()
+            assert not pipe._h2_pending and not pipe.repaired
 
 
 def test_batch_invariance_480x640(gpu_lib):

@@ -78,6 +78,14 @@ def _arithmetic_class(products: int, engine: int, amp: int, override: int):
             _lib.call("xp_set_dense_engine", found_engine)
 
 
+def take_status(word: torch.Tensor) -> int:
+    """Read a forward status word (int32[1] on the device; one 4-byte download = a host synchronisation of the current stream) and clear it."""
+    st = int(word.item())
+    if st:
+        word.zero_()
+    return st
+
+
 class XPoint(torch.nn.Module):
     # reference XPoint.py:29-59
     default_config = {
@@ -501,20 +509,14 @@ class XPoint(torch.nn.Module):
             res = self._forward_raw(images, want_prob, want_desc, want_logits, out, workspace, is_optical, status)
             if check and not torch.cuda.is_current_stream_capturing():
                 word = self.status_word(images.device) if status is None else status
-                st = int(word.item())
+                st = take_status(word)
                 if st:
-                    word.zero_()
-
                     def retry():
                         self._forward_raw(images, want_prob, want_desc, want_logits, res if out is None else out, workspace, is_optical, status)
-                        v = int(word.item())
-                        word.zero_()
-                        return v
+                        return take_status(word)
                     if self.handle_status(st, "forward", retry=retry):
                         res = self._forward_raw(images, want_prob, want_desc, want_logits, res if out is None else out, workspace, is_optical, status)
-                        st = int(word.item())
-                        word.zero_()
-                        self.handle_status(st, "forward, second run")       # raises when "x3" is non-finite as well
+                        self.handle_status(take_status(word), "forward, second run")       # raises when "x3" is non-finite as well
             return res
 
     def _forward_raw(self, images: torch.Tensor, want_prob=True, want_desc=True, want_logits=False, out=None, workspace=None,

@@ -10,12 +10,14 @@ from __future__ import annotations
 
 import copy
 import ctypes
+import os
 
 import torch
 
 from . import _lib
 from . import utils
 from ._lib import c_i, ptr
+from .models import take_status
 
 # reference configs/cipdp.yaml:47-61
 DEFAULT_PREDICTION = dict(detection_threshold=0.015, nms=8, cpu_nms=True, topk=0,
@@ -145,20 +147,21 @@ class PairPipeline:
         self.images_b = [torch.empty((n, 1, H, W), device=dev) for _ in range(nbuf)]
         self.images = self.images_b[0]
         self.raw_b = [None] * nbuf
-        self.mask_b = [None] * nbuf
+        self.mask_b = [None] * nbuf          # uint8 valid masks per buffer set: allocated by the first masked step
+        self._u8_b = None                    # uint8 image staging per buffer set: allocated by the first uint8 step
         self.prob_nms = torch.empty((n, H, W), device=dev)
         self.prob_masked = torch.empty((n, H, W), device=dev)
+        self.group_ws = self.alt_ws = None   # encoder workspaces of the split (one per image group) / alternating (one per buffer set) schedule
         if self.overlap:
             self.enc_stream, self.post_stream = torch.cuda.Stream(), torch.cuda.Stream()
+            S = max(self.split_encoder, 1)
+            n_enc = S if self.split_encoder else nbuf if self.alternate else 1         # streams that encode: one per image group / per buffer set (_streams_of)
+            self.enc_streams = [self.enc_stream] + [torch.cuda.Stream() for _ in range(n_enc - 1)]
             if self.split_encoder:
-                S = self.split_encoder
-                self.enc_streams = [self.enc_stream] + [torch.cuda.Stream() for _ in range(S - 1)]
-                self.encs_done = [[torch.cuda.Event() for _ in range(S)] for _ in range(nbuf)]
                 self.group_ws = [torch.empty(net.workspace_bytes(n // S, H, W), dtype=torch.uint8, device=dev) for _ in range(S)]
             if self.alternate:
-                self.enc_streams = [self.enc_stream] + [torch.cuda.Stream() for _ in range(nbuf - 1)]
                 self.alt_ws = [torch.empty(net.workspace_bytes(n, H, W), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
-            self.enc_done = [torch.cuda.Event() for _ in range(nbuf)]
+            self.enc_done = [[torch.cuda.Event() for _ in range(S)] for _ in range(nbuf)]      # [buffer set][image group]
             self.post_done = [torch.cuda.Event() for _ in range(nbuf)]
         self.nms_ws = torch.empty(lib.xp_box_nms_workspace_bytes(n, H, W, self.cap), dtype=torch.uint8, device=dev)
         self.kp = torch.zeros((n, self.cap, 2), dtype=torch.int32, device=dev)
@@ -187,6 +190,16 @@ class PairPipeline:
         self._last = None            # (buffer set, masked) of the latest call: what verify() re-runs when the range guard trips
         self._graphs = None
         self._capture_masked = None
+        # range guard of the dense engine (status_word, _note_engine, _settle_engine)
+        self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._engine_enqueued = None   # dense engine of the forward enqueued last
+        self._h2_pending = False       # some forward enqueued on "h2" has not been judged yet
+        self._graph_engine = None      # dense engine the graphs were captured on
+        # download_async: pinned host buffer sets (allocated by its first call) and their rotation
+        self._copy_engine_d2h = os.environ.get("XP_D2H_COPY_ENGINE", "0") == "1"      # A/B: the runtime's copy engines for the result lists
+        self.host_sets = max(2, self.depth + 1)
+        self._host = self._host_src = self._host_ev = None
+        self._host_i = 0
 
     def run(self, optical, thermal, mask_optical=None, mask_thermal=None):
         """Input contract (also of capture() / the replay callable): optical and thermal are (B, 1, H, W) / (B, H, W) images of the SAME dtype —
@@ -195,49 +208,53 @@ class PairPipeline:
         if (mask_optical is None) != (mask_thermal is None):
             raise ValueError("PairPipeline.run: pass both valid masks or neither")
         with torch.cuda.device(self.device):
-            return self._run(optical, thermal, mask_optical, mask_thermal)
+            return self._step(optical, thermal, mask_optical, mask_thermal)
 
-    def _run(self, optical, thermal, mask_optical, mask_thermal):
-        if not self.overlap:
+    def _step(self, optical, thermal, mask_optical, mask_thermal, replay=False):
+        """Enqueue one step: THE schedule, for eager steps and (replay=True) for steps replayed from the captured graphs.  The two bodies it runs —
+        the encoder on image group h of buffer set k, detection / matching on buffer set k — are eager calls or graph replays; the waits and records
+        around them are the same ("PairPipeline's step schedule")."""
+        masked = mask_optical is not None
+        if not self.overlap:                                    # one stream: everything in the caller's stream order
             self._stage_inputs(0, optical, thermal, mask_optical, mask_thermal)
-            self._last = (0, mask_optical is not None)
-            self._encode(0, None, None)
-            return self._post(0, mask_optical is not None, None)
+            self._last = (0, masked)
+            if replay:
+                self._note_engine(self._graph_engine)
+                self._graphs.replay()
+            else:
+                self._encode_group(0)
+                self._post(0, masked)
+            return self
         k = self._call % self.depth
         self._call += 1
-        self._last = (k, mask_optical is not None)
+        self._last = (k, masked)
         cur = torch.cuda.current_stream()
-        # inputs are taken over on the CALLER's stream (so the caller may reuse its tensors right after run() returns),
-        # once the call before last has finished with buffer k
+        # inputs are taken over on the CALLER's stream (so the caller may reuse its tensors right after the call returns),
+        # once the step `depth` calls ago has finished with buffer set k
         cur.wait_event(self.post_done[k])
         self._stage_inputs(k, optical, thermal, mask_optical, mask_thermal)
-        self.enc_stream.wait_stream(cur)
-        if self.split_encoder:
-            S = self.split_encoder
-            if self.raw_b[k] is None:          # allocate the full-batch outputs once; the groups write into views of them
-                with torch.cuda.stream(self.enc_stream):
-                    self._encode(k, None, None)
-                cur.wait_stream(self.enc_stream)
-            g = 2 * self.B // S
-            for h, stream in enumerate(self.enc_streams):
-                stream.wait_stream(cur)
-                with torch.cuda.stream(stream):
-                    sl = slice(h * g, (h + 1) * g)
-                    view = {kk: (v[sl] if v is not None else None) for kk, v in self.raw_b[k].items()}
-                    fl = self._flags()
-                    self.net.forward_raw(self.images_b[k][sl], want_prob=True, want_desc=True, out=view, workspace=self.group_ws[h],
-                                         is_optical=None if fl is None else fl[sl], check=False, **self._status_kw())
-                    self.encs_done[k][h].record()
-                self.post_stream.wait_event(self.encs_done[k][h])
-        else:
-            stream = self.enc_streams[k] if self.alternate else self.enc_stream
+        enc_g, post_g = self._graphs[k] if replay else (None, None)
+        if self.split_encoder and self.raw_b[k] is None:        # first (eager) step on this buffer set: one whole-batch forward allocates the outputs the groups write into
+            self.enc_stream.wait_stream(cur)
+            with torch.cuda.stream(self.enc_stream):
+                self._encode_group(k)
+            cur.wait_stream(self.enc_stream)
+        for h, stream in enumerate(self._streams_of(k)):
             stream.wait_stream(cur)
             with torch.cuda.stream(stream):
-                self._encode(k, None, None)
-                self.enc_done[k].record()
-            self.post_stream.wait_event(self.enc_done[k])
+                if replay:
+                    self._note_engine(self._graph_engine)
+                    enc_g[h].replay()
+                else:
+                    self._encode_group(k, h)
+                self.enc_done[k][h].record()
+            self.post_stream.wait_event(self.enc_done[k][h])
         with torch.cuda.stream(self.post_stream):
-            self._post(k, mask_optical is not None, None)
+            if replay:
+                post_g.replay()
+                self.raw, self.images = self.raw_b[k], self.images_b[k]      # (what _post sets)
+            else:
+                self._post(k, masked)
             self.post_done[k].record()
         return self
 
@@ -274,7 +291,7 @@ class PairPipeline:
         if optical.dtype == torch.uint8:
             # 8-bit gray images (what a camera / decoder delivers): a quarter of the bytes over PCIe, gray / 255 on the device — the same f32 division the
             # reference's loader does on the host (xpoint/datasets/ImagePairDataset.py:254-274), so the staged images are the same bits
-            if getattr(self, "_u8_b", None) is None:
+            if self._u8_b is None:
                 self._u8_b = [torch.empty((2 * B, H, W), dtype=torch.uint8, device=img.device) for _ in range(self.depth)]
             u8 = self._u8_b[k]
             u8[:B].copy_(optical.reshape(B, H, W), non_blocking=True)
@@ -287,16 +304,25 @@ class PairPipeline:
             self.mask_b[k][:B].copy_(mask_optical.reshape(B, H, W))
             self.mask_b[k][B:].copy_(mask_thermal.reshape(B, H, W))
 
-    def _encode(self, k, optical, thermal):
-        if optical is not None:
-            self._stage_inputs(k, optical, thermal, None, None)
-        ws = self.alt_ws[k] if getattr(self, "alternate", False) else None
+    def _encode_group(self, k, h=None):
+        """Enqueue the encoder + heads on image group h of buffer set k, on the current stream.  h=None, or a schedule with one group: the whole batch
+        (also what the allocating first step of the split schedule and a range-guard repair run)."""
+        fl = self._flags()
+        whole = h is None or not self.split_encoder
+        if whole:
+            img, out, ws = self.images_b[k], self.raw_b[k], self.alt_ws[k] if self.alternate else None
+        else:
+            g = 2 * self.B // self.split_encoder
+            sl = slice(h * g, (h + 1) * g)
+            img, ws, fl = self.images_b[k][sl], self.group_ws[h], None if fl is None else fl[sl]
+            out = {kk: (v[sl] if v is not None else None) for kk, v in self.raw_b[k].items()}      # the group writes into views of the full-batch outputs
         # check=False: stream-ordered, no host synchronisation here; the forward's status word is read in verify() / fetch() / download_async()
         self._note_engine()
-        self.raw_b[k] = self.net.forward_raw(self.images_b[k], want_prob=True, want_desc=True, out=self.raw_b[k], workspace=ws, is_optical=self._flags(),
-                                             check=False, **self._status_kw())
+        res = self.net.forward_raw(img, want_prob=True, want_desc=True, out=out, workspace=ws, is_optical=fl, check=False, status=self._status)
+        if whole:
+            self.raw_b[k] = res
 
-    def _post(self, k, masked=False, _unused=None):
+    def _post(self, k, masked=False):
         B, H, W, n = self.B, self.H, self.W, 2 * self.B
         lib = _lib.load()
         st = _lib.current_stream()
@@ -371,45 +397,17 @@ class PairPipeline:
         for the other case."""
         with torch.cuda.device(self.device):
             for _ in range(self.depth):                         # warm-up outside capture: one-time allocations, every buffer set
-                self._run(optical, thermal, mask_optical, mask_thermal)
+                self._step(optical, thermal, mask_optical, mask_thermal)
             torch.cuda.synchronize()
             self._settle_engine()                               # a range-guard trip during warm-up switches the engine BEFORE anything is captured
             self._capture_masked = mask_optical is not None
             self._capture_graphs()
-            if not self.overlap:
-                def replay(optical, thermal, mask_optical=None, mask_thermal=None):
-                    self._check_replay_masks(mask_optical, mask_thermal)
-                    self._stage_inputs(0, optical, thermal, mask_optical, mask_thermal)
-                    self._last = (0, mask_optical is not None)
-                    self._note_engine(self._graph_engine)
-                    self._graphs.replay()
-                    return self
-                return replay
 
-            def replay(optical, thermal, mask_optical=None, mask_thermal=None):
-                self._check_replay_masks(mask_optical, mask_thermal)
-                with torch.cuda.device(self.device):
-                    k = self._call % self.depth
-                    self._call += 1
-                    self._last = (k, mask_optical is not None)
-                    cur = torch.cuda.current_stream()
-                    cur.wait_event(self.post_done[k])
-                    self._stage_inputs(k, optical, thermal, mask_optical, mask_thermal)
-                    enc_g, pg = self._graphs[k]
-                    self._note_engine(self._graph_engine)
-                    for h, stream in enumerate(self._streams_of(k)):
-                        stream.wait_stream(cur)
-                        with torch.cuda.stream(stream):
-                            enc_g[h].replay()
-                            self.encs_done[k][h].record() if self.split_encoder else self.enc_done[k].record()
-                        self.post_stream.wait_event(self.encs_done[k][h] if self.split_encoder else self.enc_done[k])
-                    with torch.cuda.stream(self.post_stream):
-                        pg.replay()
-                        self.post_done[k].record()
-                    self.raw = self.raw_b[k]
-                    self.images = self.images_b[k]
-                return self
-            return replay
+        def replay(optical, thermal, mask_optical=None, mask_thermal=None):
+            self._check_replay_masks(mask_optical, mask_thermal)
+            with torch.cuda.device(self.device):
+                return self._step(optical, thermal, mask_optical, mask_thermal, replay=True)
+        return replay
 
     def _check_replay_masks(self, mask_optical, mask_thermal):
         if (mask_optical is None) != (mask_thermal is None):
@@ -425,36 +423,27 @@ class PairPipeline:
     def _capture_graphs(self):
         """(Re)capture the step's graphs with the dense engine in force now; buffers exist (warm-up done), device synchronised."""
         masked = self._capture_masked
-        self._graph_engine = self.net.effective_gemm_mode() if hasattr(self.net, "effective_gemm_mode") else None      # what every replay enqueues (_note_engine)
-        pend = getattr(self, "_h2_pending", False)
+        self._graph_engine = self.net.effective_gemm_mode()     # what every replay enqueues (_note_engine)
+        pend = self._h2_pending
         if not self.overlap:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._encode(0, None, None)
-                self._post(0, masked, None)
+                self._encode_group(0)
+                self._post(0, masked)
             self._graphs = g
             self._h2_pending = pend                             # (capturing enqueues nothing)
             return
-        S = max(self.split_encoder, 1)
         graphs = []
         for k in range(self.depth):
             enc_g = []
-            gsz = 2 * self.B // S
             for h, stream in enumerate(self._streams_of(k)):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=stream):
-                    if self.split_encoder:
-                        sl = slice(h * gsz, (h + 1) * gsz)
-                        view = {kk: (v[sl] if v is not None else None) for kk, v in self.raw_b[k].items()}
-                        fl = self._flags()
-                        self.net.forward_raw(self.images_b[k][sl], want_prob=True, want_desc=True, out=view, workspace=self.group_ws[h],
-                                             is_optical=None if fl is None else fl[sl], check=False, **self._status_kw())
-                    else:
-                        self._encode(k, None, None)
+                    self._encode_group(k, h)
                 enc_g.append(g)
             pg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(pg, stream=self.post_stream):
-                self._post(k, masked, None)
+                self._post(k, masked)
             graphs.append((enc_g, pg))
         self._graphs = graphs
         self._h2_pending = pend                                 # (capturing enqueues nothing)
@@ -463,71 +452,50 @@ class PairPipeline:
     def status_word(self):
         """This pipeline's OWN forward status word (int32[1] on its device): its forwards OR their XP_STATUS_* bits into it and only its own
         verify() / fetch() reads and clears it — another pipeline on the same model, or an eager forward, cannot consume a trip raised by a step
-        that is still in flight here.  Models without a status word (the conv back-bones) get the model's shared behaviour."""
-        if getattr(self, "_status", None) is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        that is still in flight here."""
         return self._status
-
-    def _status_kw(self):
-        import inspect
-        if not hasattr(self, "_status_ok"):
-            self._status_ok = hasattr(self.net, "status_word") and "status" in inspect.signature(self.net.forward_raw).parameters
-        return {"status": self.status_word()} if self._status_ok else {}
 
     def _note_engine(self, engine=None):
         """Record the dense engine of the forwards this pipeline enqueues (eager: the model's engine now; graph replay: the engine the graphs were
         captured on): a status trip is judged against THAT engine, not against whatever the shared model has been switched to since (_settle_engine)."""
         if engine is None:
-            engine = self.net.effective_gemm_mode() if hasattr(self.net, "effective_gemm_mode") else None
+            engine = self.net.effective_gemm_mode()
         if engine == "h2":
             self._h2_pending = True
         self._engine_enqueued = engine
-
-    def _handle_status_params(self):
-        if getattr(self, "_hs_params", None) is None:
-            import inspect
-            self._hs_params = set(inspect.signature(self.net.handle_status).parameters)
-        return self._hs_params
 
     def _settle_engine(self):
         """After a device-wide synchronisation: read and clear the forward status word.  Non-zero on the split-fp16 engine = an operand left
         the fp16 range: the model switches to "x3" for this weight set (warning), captured graphs are re-captured on it, and the latest call
         is computed again from its staged inputs — the results the caller reads next are never the overflowed ones.  Non-zero on any other
         engine raises (models.XPoint.handle_status).  Returns True when it re-ran."""
-        if not hasattr(self.net, "status_word"):
-            return False
-        word = self.status_word()
-        st = int(word.item())
+        word = self._status
+        st = take_status(word)
         if st == 0:
             self._h2_pending = False                           # (device-wide synchronisation done: nothing enqueued on h2 is still in flight)
             return False
-        word.zero_()
         # judged against the engine the pending forwards were enqueued with (some step in flight on "h2" -> recoverable, even when another user of
         # the same model has already switched it to "x3"); raises unless the h2 -> x3 switch applies
-        pending = "h2" if getattr(self, "_h2_pending", False) else getattr(self, "_engine_enqueued", None)
+        pending = "h2" if self._h2_pending else self._engine_enqueued
         self._h2_pending = False
         retry = None
         if self._last is not None:
             def retry():          # the latest call's forward again (eager, from its staged inputs) on the model's current settings -> its status
-                self._encode(self._last[0], None, None)
+                self._encode_group(self._last[0])
                 torch.cuda.synchronize()
-                v = int(word.item())
-                word.zero_()
-                return v
+                return take_status(word)
         # round 6: on "h2" the model first tries to LOCALISE the trip (only the out-of-range launches move to the x3 planes) before giving up the engine
-        self.net.handle_status(st, "PairPipeline", pending, **({"retry": retry} if retry is not None and "retry" in self._handle_status_params() else {}))
+        self.net.handle_status(st, "PairPipeline", pending, retry=retry)
         self._h2_pending = False                               # (the localisation's forwards were synchronised and read by retry())
         if self._graphs is not None:
             self._capture_graphs()
         if self._last is not None:
             k, masked = self._last
-            self._encode(k, None, None)
-            self._post(k, masked, None)
+            self._encode_group(k)
+            self._post(k, masked)
             torch.cuda.synchronize()
-            st = int(word.item())
-            word.zero_()
             self._h2_pending = False
-            self.net.handle_status(st, "PairPipeline, second run")
+            self.net.handle_status(take_status(word), "PairPipeline, second run")
         return True
 
     def download_async(self):
@@ -538,38 +506,36 @@ class PairPipeline:
         may keep `depth` steps in flight and must consume a set before the host_sets-th call after it).  The copies are ordered on the stream that
         writes the results, ahead of the next step's kernels."""
         with torch.cuda.device(self.device):
-            if not hasattr(self, "_host"):
+            if self._host is None:
                 def pin(t):
                     return torch.empty(t.shape, dtype=t.dtype, device="cpu").pin_memory()
                 src = dict(counts=self.counts, kp=self.kp, match_count=self.m["match_count"], match_q=self.m["match_q"], match_t=self.m["match_t"],
                            match_d=self.m["match_d"])
-                if hasattr(self.net, "status_word"):
-                    src["status"] = self.status_word()                     # XP_STATUS_* bits of THIS pipeline's forwards so far: non-zero = call verify()
+                src["status"] = self._status                               # XP_STATUS_* bits of THIS pipeline's forwards so far: non-zero = call verify()
                 if self.estimate_homography:
                     src.update(H_est=self.hg["H"], n_inliers=self.hg["n_inliers"], matchesMask=self.hg["mask"])
                 self._host_src = src
-                import os
-                self._copy_engine_d2h = os.environ.get("XP_D2H_COPY_ENGINE", "0") == "1"      # A/B: the runtime's copy engines for the result lists
-                self.host_sets = max(2, self.depth + 1)
                 self._host = [{k: pin(v) for k, v in src.items()} for _ in range(self.host_sets)]
                 self._host_ev = [torch.cuda.Event() for _ in range(self.host_sets)]
-                self._host_i = 0
             i = self._host_i
             self._host_i = (i + 1) % self.host_sets
             stream = self.post_stream if self.overlap else torch.cuda.current_stream()
             with torch.cuda.stream(stream):
-                # by a kernel, not by the copy engines: a device-to-host copy queued behind this step's kernels would hold up the NEXT steps' image
-                # uploads in the engines' queue (xp_copy_to_mapped_host; bench.py's streaming loop: 1 553 -> see profiles/r5_streaming_parts.txt)
-                lib = _lib.load()
                 for k, v in self._host_src.items():
-                    h = self._host[i][k]
-                    if v.is_contiguous() and v.numel() > 0 and v.data_ptr() % 16 == 0 and h.data_ptr() % 16 == 0 and not self._copy_engine_d2h:
-                        _lib.check(lib.xp_copy_to_mapped_host(ctypes.c_void_p(v.data_ptr()), ctypes.c_void_p(h.data_ptr()), v.numel() * v.element_size(),
-                                                              _lib.current_stream()), "xp_copy_to_mapped_host")
-                    else:
-                        h.copy_(v, non_blocking=True)
+                    self.copy_to_pinned(v, self._host[i][k])
                 self._host_ev[i].record()
             return self._host[i], self._host_ev[i]
+
+    def copy_to_pinned(self, v, h):
+        """Enqueue the copy of device tensor v into pinned host tensor h on the current stream.
+        By a kernel, not by the copy engines: a device-to-host copy queued behind this step's kernels would hold up the NEXT steps' image
+        uploads in the engines' queue (xp_copy_to_mapped_host; bench.py's streaming loop: 1 553 -> see profiles/r5_streaming_parts.txt).  Tensors the
+        kernel does not take (non-contiguous, empty, not 16-byte aligned) and XP_D2H_COPY_ENGINE=1 (A/B) go through the runtime's copy."""
+        if v.is_contiguous() and v.numel() > 0 and v.data_ptr() % 16 == 0 and h.data_ptr() % 16 == 0 and not self._copy_engine_d2h:
+            _lib.check(_lib.load().xp_copy_to_mapped_host(ctypes.c_void_p(v.data_ptr()), ctypes.c_void_p(h.data_ptr()), v.numel() * v.element_size(),
+                                                          _lib.current_stream()), "xp_copy_to_mapped_host")
+        else:
+            h.copy_(v, non_blocking=True)
 
     def verify(self):
         """After a synchronisation point: the async NMS must have reached its fixed point and no list may have
@@ -600,7 +566,7 @@ class PairPipeline:
                 if self._graphs is not None:
                     self._capture_graphs()
                 k, masked = self._last
-                self._post(k, masked, None)
+                self._post(k, masked)
                 torch.cuda.synchronize()
                 _lib.check(lib.xp_box_nms_check(ptr(self.nms_ws), 2 * self.B, self.H, self.W, ctypes.byref(left), _lib.current_stream()),
                            "xp_box_nms_check")

@@ -8,12 +8,11 @@ steps in flight (depth + 1 pinned buffer sets rotate): it consumes step i - dept
 reference fixtures g15 (lists) and g21 (hm)."""
 from __future__ import annotations
 
-import ctypes
 import os
 
 import torch
 
-from . import _lib
+from .models import take_status
 from .predict import PairPipeline
 
 CROP = 256
@@ -38,7 +37,7 @@ class StreamingRegistrationStep:
             with torch.cuda.graph(self.graph):
                 self.hm = net_hm.predict_homography(self.crop_o, self.crop_t)
             self._hm_engine = net_hm.effective_gemm_mode()
-            self.host_sets = max(2, pipe.depth + 1)         # as PairPipeline.download_async: `depth` steps may be in flight on the host side
+            self.host_sets = pipe.host_sets                 # as PairPipeline.download_async: `depth` steps may be in flight on the host side
             self.hm_host = [torch.empty(self.hm.shape, dtype=self.hm.dtype).pin_memory() for _ in range(self.host_sets)]
             self.hm_ev = [torch.cuda.Event() for _ in range(self.host_sets)]
         self._i = 0
@@ -67,11 +66,7 @@ class StreamingRegistrationStep:
                 j = self._i % self.host_sets
                 self._i += 1
                 # like the result lists (PairPipeline.download_async): by a kernel, so that no copy-engine transfer of this step queues ahead of the next uploads
-                if self.hm.is_contiguous() and self.hm.data_ptr() % 16 == 0 and not getattr(pipe, "_copy_engine_d2h", False):
-                    _lib.check(_lib.load().xp_copy_to_mapped_host(ctypes.c_void_p(self.hm.data_ptr()), ctypes.c_void_p(self.hm_host[j].data_ptr()),
-                                                                  self.hm.numel() * self.hm.element_size(), _lib.current_stream()), "xp_copy_to_mapped_host")
-                else:
-                    self.hm_host[j].copy_(self.hm, non_blocking=True)
+                pipe.copy_to_pinned(self.hm, self.hm_host[j])
                 self.hm_ev[j].record()
                 if pipe.overlap and not self._head_on_caller:
                     pipe.post_done[pipe._last[0]].record()
@@ -84,18 +79,14 @@ class StreamingRegistrationStep:
         torch.cuda.synchronize()
         self.pipe.verify()
         word = self.net_hm.status_word(self.pipe.device)
-        st = int(word.item())
+        st = take_status(word)
         if st:
-            word.zero_()
-
             def retry():          # the head's forward again, eagerly, on the model's current settings -> its status (round 6: the trip is localised first)
                 with torch.cuda.device(self.pipe.device), torch.no_grad():
                     flags = [True] * self.B + [False] * self.B if self.net_hm.config['multispectral'] else None      # as predict_homography
                     self.net_hm.forward_raw(torch.cat([self.crop_o, self.crop_t], 0), want_prob=False, want_desc=False, is_optical=flags, check=False)
                     torch.cuda.synchronize()
-                v = int(word.item())
-                word.zero_()
-                return v
+                return take_status(word)
             if self.net_hm.handle_status(st, "StreamingRegistrationStep head", retry=retry):
                 with torch.cuda.device(self.pipe.device), torch.no_grad():
                     self.graph = torch.cuda.CUDAGraph()
