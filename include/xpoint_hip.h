@@ -785,6 +785,32 @@ int xp_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, float* dx
 int xp_add_scaled_rows(const float* x, const float* r, const float* s, float* y, int batch, int64_t rows_per_sample, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The SS2D core of VSS-block training in pixel layout (xpoint_amd/training/ops.py ss2d_core, the block's `ss2d_core = "pixel"`; csrc/train_ss2d.hip;
+ * DESIGN.md section 24): cross-scan, the four-route selective scan (d_state 1, softplus, D and dt bias) and cross-merge as ONE operator that reads and
+ * writes rows of the (batch, H, W) pixel grid only — no (batch, 4, C, L) tensor anywhere.  M = batch H W, f32, contiguous unless a stride is named:
+ *   u (M, C); dtp (M, 4, C) the dt projection BEFORE bias and softplus; bc: the B / C pair of pixel m and route k at bc[m bc_ld + k bc_kstride + {0, 1}]
+ *   (the x_proj row (M, 4, R + 2) itself: bc = row + R, bc_ld = 4 (R + 2), bc_kstride = R + 2); A = -exp(A_logs), Ds, dt_bias: (4, C).
+ *   Route k in the reference's order (0 row-major, 1 column-major, 2 and 3 their reverses).
+ * xp_ss2d_train_fwd: ym (M, C) = (y_0 + y_2) + (y_1 + y_3), xp_cross_merge's order of additions.  It leaves the state entering every chunk of every
+ *   route and the chunk's decay product in the workspace, which is all the backward needs of the forward: hand the SAME workspace, untouched, to
+ *   xp_ss2d_train_bwd with the same inputs, shape and chunk.
+ * xp_ss2d_train_bwd: from dym (M, C): du (M, C), ddtp (M, 4, C), dbc (M, 4, 2) = (dB, dC) per pixel and route, dA, dD, ddt_bias (4, C) each (dA is the
+ *   gradient of A, not of A_logs).  h is rebuilt per chunk in LDS.
+ * chunk: the number of route steps a workgroup owns: 0 = the library's choice (16 up to C = 128, 8 up to C = 512, 4 above), else a power
+ *   of two in [2, 64] with chunk C <= 6144.  An argument of the call, not a process-wide setting; results of different chunks agree to rounding.
+ * No atomics: two calls are bit-identical; ym, du, ddtp and dbc of a sample do not depend on the other samples of the call; an all-zero dym gives
+ *   all-zero gradients; dA / dD / ddt_bias add per-(sample, chunk) partials in that order in f64.  batch in [1, 65535], C in [1, 1024],
+ *   batch H W 4 C < 2^31 (32-bit element offsets), dstate must be 1.  Workspace: xp_ss2d_train_workspace_bytes(batch, H, W, C, chunk) (0 for
+ *   arguments the entry points refuse), 256-byte aligned. */
+size_t xp_ss2d_train_workspace_bytes(int batch, int H, int W, int C, int chunk);
+int xp_ss2d_train_fwd(const float* u, const float* dtp, const float* bc, int64_t bc_ld, int64_t bc_kstride, const float* A, const float* Ds,
+                      const float* dt_bias, float* ym, void* workspace, size_t workspace_bytes, int batch, int H, int W, int C, int dstate, int chunk,
+                      void* stream);
+int xp_ss2d_train_bwd(const float* u, const float* dtp, const float* bc, int64_t bc_ld, int64_t bc_kstride, const float* A, const float* Ds,
+                      const float* dt_bias, const float* dym, float* du, float* ddtp, float* dbc, float* dA, float* dD, float* ddt_bias,
+                      void* workspace, size_t workspace_bytes, int batch, int H, int W, int C, int dstate, int chunk, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training of the whole VMamba encoder (xpoint_amd/training/encoder.py VSSEncoder; csrc/train_dense.hip (weight gradients), csrc/train_dgrad.hip (input gradient), csrc/elementwise.hip; DESIGN.md section 19;
  * reference VMamba.py:1405-1440 patch embed and downsample v3, :1507-1525 VSSM.forward): the strided layers between the VSS blocks.  The convolution
  * is 3x3, ZERO padding 1, STRIDE 2: x (batch, H, W, Ci), y / dy (batch, Ho, Wo, Co) with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, w (Co, 3, 3, Ci).

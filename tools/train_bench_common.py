@@ -42,13 +42,18 @@ def kernel_split(step):
     return dict(sorted(rows.items(), key=lambda kv: -kv[1]["us"]))
 
 
-def alternate(res, step_hip, step_eager, iters):
-    """Fill `res` with both sides' times, peak memory and host issue time — hip, eager, hip, eager — and their ratio."""
+def alternate(res, step_hip, step_eager, iters, tags=("hip", "eager")):
+    """Fill `res` with both sides' times, peak memory and host issue time — hip, eager, hip, eager — and their ratio.  tags: the two sides' names (two
+    forms of the HIP side against each other: ("pixel", "routes"))."""
+    a, b = tags
     for rep in range(2):
-        for tag, st in (("hip", step_hip), ("eager", step_eager)):
+        for tag, st in ((a, step_hip), (b, step_eager)):
             ms, mib = measure(st, iters)
             res.setdefault(f"{tag}_fwd_bwd_ms", []).append(round(ms, 4))
             res[f"{tag}_peak_MiB"] = round(mib, 1)
             res[f"{tag}_host_issue_ms"] = round(measure.host_ms, 4)
-    res["ratio_hip_over_eager"] = round(min(res["hip_fwd_bwd_ms"]) / min(res["eager_fwd_bwd_ms"]), 3)
+    res[f"ratio_{a}_over_{b}"] = round(min(res[f"{a}_fwd_bwd_ms"]) / min(res[f"{b}_fwd_bwd_ms"]), 3)
+    if tags != ("hip", "eager"):
+        for tag in tags:
+            res[f"{tag}_spread"] = round((max(res[f"{tag}_fwd_bwd_ms"]) - min(res[f"{tag}_fwd_bwd_ms"])) / min(res[f"{tag}_fwd_bwd_ms"]), 3)
     return res

@@ -2,7 +2,7 @@
 and the heads, XPointLoss, backward into every parameter, Adam) against torch eager autograd of the same model, f32, on the same GPU; and the input
 gradient of the reflection-padded 3x3 convolution against what the operators could do before it existed.
 
-    python tools/xpoint_train_bench.py [--iters 5] [--batch 16] [--size 256] [--only kernel|step]
+    python tools/xpoint_train_bench.py [--iters 5] [--batch 16] [--size 256] [--only kernel|step] [--core routes|pixel|both]
 
 (a) Kernel: conv3x3_dgrad_reflect at the trunk's shapes, dy (batch, size / 8, size / 8, 512), Ci 48 (VMamba) and 128 (conv encoder), against the
 composition: dy copied into a zero (H + 2) x (W + 2) frame, conv3x3_dgrad (the zero-padded input gradient) on the frame, the frame folded back with
@@ -12,7 +12,9 @@ three runs.  A call takes well under a millisecond, so this part runs 40 x --ite
 both sides.  The eager side is tools/encoder_train_bench.py's eager encoder (its selective scan and cross scan / merge bound to xpoint_amd.kernels,
 the only way the reference trains on ROCm), the heads' torch modules (ReflectionPad2d, Conv2d, ReLU, BatchNorm2d, Conv2d, BatchNorm2d, F.normalize)
 and the same XPointLoss and Adam.  The method is tools/train_bench_common.py's: device events after a warm-up, the host's issue time next to them,
-then the HIP side's per-kernel split from the library's event profiler.  One JSON line per measurement; nothing is asserted."""
+then the HIP side's per-kernel split from the library's event profiler.  --core: the form of the HIP model's SS2D cores (training.set_ss2d_core;
+default routes); `both`: the model under "pixel" against the model under "routes" instead of against eager, alternating in the same call, with each
+side's spread over its two rounds and both kernel splits.  One JSON line per measurement; nothing is asserted."""
 import argparse
 import copy
 import json
@@ -87,14 +89,14 @@ def eager_model(model, data):
     return preds
 
 
-def bench_step(batch, size, iters):
+def bench_step(batch, size, iters, core="routes"):
     cfg = synth.xpoint_exp1_config(size, size)
     cfg["mixed_precision"] = False
     cfg["use_attention"]["model_parameters"]["MODEL"]["DROP_PATH_RATE"] = 0.0
     net = models.XPoint(cfg)
     net.load_state_dict(synth.make_torch_state_dict(cfg))
-    hip = training.XPointNet.from_model(net).cuda().train()
-    eager = copy.deepcopy(hip)
+    hip = training.set_ss2d_core(training.XPointNet.from_model(net), "pixel" if core == "both" else core).cuda().train()
+    eager = training.set_ss2d_core(training.XPointNet.from_model(net), "routes").cuda().train() if core == "both" else copy.deepcopy(hip)
     data = pair_batch(batch, size)
     loss_fn = losses.XPointLoss(LOSS_CFG)
     opts = {id(m): torch.optim.Adam(m.parameters(), lr=1e-5) for m in (hip, eager)}
@@ -115,7 +117,20 @@ def bench_step(batch, size, iters):
 
     enc = hip._encoders["encoder."]
     res = {"what": "XPoint train_step (2 spectra fwd+bwd, loss, Adam)", "embed_dim": enc.embed_dim, "depths": enc.depths, "images": [2, batch, 1, size, size],
-           "iters": iters, "parameters": sum(p.numel() for p in hip.parameters())}
+           "iters": iters, "core": core, "parameters": sum(p.numel() for p in hip.parameters())}
+    if core == "both":
+        def step_routes():
+            torch.manual_seed(3)
+            last["routes"], _ = training.train_step(eager, data, loss_fn, opts[id(eager)])
+        alternate(res, step_hip, step_routes, iters, tags=("pixel", "routes"))
+        res["last_loss"] = {"pixel": float(last["hip"]), "routes": float(last["routes"])}
+        for tag, st in (("pixel", step_hip), ("routes", step_routes)):
+            split = kernel_split(st)
+            res[f"{tag}_kernel_ms"] = round(sum(v["us"] for v in split.values()) / 1e3, 3)
+            res[f"{tag}_launches"] = sum(v["launches"] for v in split.values())
+            res[f"{tag}_kernel_split_top"] = dict(list(split.items())[:14])
+        print(json.dumps(res), flush=True)
+        return
     alternate(res, step_hip, step_eager, iters)
     res["last_loss"] = {k: float(v) for k, v in last.items()}          # both sides took the same number of steps from the same state
     split = kernel_split(step_hip)
@@ -131,11 +146,12 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--only", choices=("kernel", "step"), default=None)
+    ap.add_argument("--core", choices=("routes", "pixel", "both"), default="routes")
     args = ap.parse_args()
     if args.only != "step":
         bench_kernel(args.batch, args.size, 40 * args.iters)          # a call takes ~0.2 ms: 40 x the iterations for a window of tens of ms
     if args.only != "kernel":
-        bench_step(args.batch, args.size, args.iters)
+        bench_step(args.batch, args.size, args.iters, args.core)
 
 
 if __name__ == "__main__":

@@ -145,6 +145,8 @@ _SIGNATURES = {
     "xp_gelu_fwd": [c_p, c_p, c_l, c_p],
     "xp_gelu_bwd": [c_p, c_p, c_p, c_l, c_p, c_p, c_sz, c_p],
     "xp_add_scaled_rows": [c_p] * 4 + [c_i, c_l, c_i, c_p],
+    "xp_ss2d_train_fwd": [c_p] * 3 + [c_l, c_l] + [c_p] * 5 + [c_sz] + [c_i] * 6 + [c_p],
+    "xp_ss2d_train_bwd": [c_p] * 3 + [c_l, c_l] + [c_p] * 11 + [c_sz] + [c_i] * 6 + [c_p],
     "xp_conv3x3_s2_wgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
     "xp_conv3x3_s2_dgrad_h2": [c_p] * 3 + [c_i] * 5 + [c_p, c_p, c_sz, c_p],
     "xp_stem_conv": [c_p] * 4 + [c_i] * 4 + [c_p],
@@ -199,6 +201,7 @@ _SIZE_QUERIES = {
     "xp_scale_grad_workspace_bytes": (c_sz, []),
     "xp_layernorm_bwd_workspace_bytes": (c_sz, [c_l, c_i]),
     "xp_dwconv3x3_silu_bwd_workspace_bytes": (c_sz, [c_i] * 4),
+    "xp_ss2d_train_workspace_bytes": (c_sz, [c_i] * 5),
     "xp_conv3x3_s2_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),
     "xp_stem_conv_wgrad_workspace_bytes": (c_sz, [c_i]),
     "xp_conv3x3_rp_dgrad_h2_workspace_bytes": (c_sz, [c_i] * 5),

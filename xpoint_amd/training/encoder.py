@@ -99,6 +99,7 @@ class VSSEncoder(TrainModule):
         self.prefix = encoder
         self.mlp_ratio = float(mlp_ratio)
         self.rates = drop_path_rates(self.depths, drop_path_rate)
+        self.ss2d_core = "routes"          # the form of every block's SS2D core in training: 'routes' or 'pixel' (training.set_ss2d_core)
         nn = torch.nn
         root = nn.Module()          # parameter containers with the reference's names and order; forward() never calls them
         pe = nn.Module()
@@ -190,7 +191,8 @@ class VSSEncoder(TrainModule):
                     r = x.reshape(B * h * w, C)
                     r = _SsmBranchFn.apply(r, s1, (B, h, w), t(p + "norm.weight"), t(p + "norm.bias"), t(p + "op.x_proj_weight"), t(p + "op.A_logs"),
                                            t(p + "op.Ds"), t(p + "op.dt_projs_weight"), t(p + "op.dt_projs_bias"), t(p + "op.out_norm.weight"),
-                                           t(p + "op.out_norm.bias"), t(p + "op.in_proj.weight"), t(p + "op.conv2d.weight"), t(p + "op.out_proj.weight"))
+                                           t(p + "op.out_norm.bias"), t(p + "op.in_proj.weight"), t(p + "op.conv2d.weight"), t(p + "op.out_proj.weight"),
+                                           self.ss2d_core if self.training else "routes")
                     r = _MlpBranchFn.apply(r, s2, B, t(p + "norm2.weight"), t(p + "norm2.bias"), t(p + "mlp.fc1.weight"), t(p + "mlp.fc1.bias"),
                                            t(p + "mlp.fc2.weight"), t(p + "mlp.fc2.bias"))
                     x = r.view(B, h, w, C)

@@ -7,7 +7,8 @@ Config keys, the reference's: training.{output_directory, n_epochs, learningrate
 training.scheduler.{use_scheduler, type: StepLR | ExponentialLR, step_size, gamma}, training.validation.{compute_validation_loss, every_nth_epoch,
 keypoints}; `num_worker` and `allow_gpu` are accepted and ignored; `training.mixed_precision: true` is refused with XPointNet's message.  New,
 optional: training.validation.foldername (the folder-mode counterpart of the reference's `filename`), training.log_every (a `batch_loss` record every
-that many steps), training.max_norm (global-norm clipping, off by default as in the reference).
+that many steps), training.max_norm (global-norm clipping, off by default as in the reference), training.ss2d_core ('routes', the default, or 'pixel':
+training.set_ss2d_core; checked before anything is built and written into params.yaml).
 
 What is kept from train.py: params.yaml with the four sections at the start; the weights of -w loaded with strict=False after
 fix_model_weigth_keys, zero loaded keys refused; the start epoch parsed from an `e<N>.model` name; loss.space_to_depth_ratio from the model; Adam with
@@ -41,7 +42,9 @@ import yaml
 
 from .. import _lib
 from .model import MIXED_PRECISION_REFUSAL, XPointNet, train_step
+from .ops import check_ss2d_core
 from .optim import Adam
+from .vss import set_ss2d_core
 
 
 def _start_epoch(weight_file):
@@ -84,6 +87,7 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
     tr = config['training']
     if tr.get('mixed_precision', False):
         raise NotImplementedError(MIXED_PRECISION_REFUSAL)
+    core = check_ss2d_core(tr.get('ss2d_core', 'routes'), "fit: training.ss2d_core")
     net = getattr(models, config['model'].get('type', 'XPoint'))(config['model'])
     XPointNet.check_config(net.config)
     device = torch.device(device)
@@ -93,7 +97,7 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
     out_dir = str(tr['output_directory'])
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, 'params.yaml'), 'wt') as fh:
-        yaml.safe_dump({'model': config['model'], 'loss': config['loss'], 'training': config['training'], 'dataset': config['dataset']}, fh)
+        yaml.safe_dump({'model': config['model'], 'loss': config['loss'], 'training': dict(config['training'], ss2d_core=core), 'dataset': config['dataset']}, fh)
 
     ds_cfg = copy.deepcopy(config['dataset'])
     aug_cfg = ds_cfg.pop('augmentation', None) or {}
@@ -118,7 +122,7 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
     print('Training on device: {}'.format(device))
 
     with torch.cuda.device(device):
-        model = XPointNet.from_model(net).to(device).train()
+        model = set_ss2d_core(XPointNet.from_model(net), core).to(device).train()
         has_hm = any(k.startswith("hm_regressor.") for k, _ in model.named_parameters())
         loss_cfg = {k: v for k, v in config['loss'].items() if k != 'type'}
         loss_cfg['space_to_depth_ratio'] = net.get_encoder_downsample_ratio()

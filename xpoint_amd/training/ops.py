@@ -1,5 +1,5 @@
 """The operator level of xpoint_amd.training: one wrapper per training kernel of the HIP library (csrc/train_dense.hip, csrc/train_dgrad.hip, csrc/train_regnet.hip,
-csrc/train_vss.hip), the forward launches the autograd functions share, and the base of the three trainable modules.  There is no CPU fallback.
+csrc/train_vss.hip, csrc/train_ss2d.hip), the forward launches the autograd functions share, and the base of the three trainable modules.  There is no CPU fallback.
 
 The public wrappers (`gemm_tn` ... `scale_grad`, re-exported by the package) check every operand — float32, on the GPU, one device — allocate outputs and
 workspace and make ONE library call; the tests pin them one by one.  The underscore helpers are the forward engine's launches as the autograd functions
@@ -425,6 +425,97 @@ def add_scaled_rows(x, r, s, stream=None):
     B, C = r.shape[0], r.shape[-1]
     _launch("xp_add_scaled_rows", r, stream, ptr(x), ptr(r), ptr(s.contiguous()), ptr(y), B, r.numel() // (B * C), C)
     return y
+
+
+SS2D_CORES = ("routes", "pixel")
+
+
+def check_ss2d_core(kind, who):
+    """The name of a form of the training SS2D core: 'routes' (the cross-scan / selective-scan / cross-merge composition) or 'pixel' (ss2d_core)."""
+    if kind not in SS2D_CORES:
+        raise ValueError(f"{who}: ss2d_core must be 'routes' or 'pixel' (got {kind!r})")
+    return kind
+
+
+def ss2d_takes_pixel(B, H, W, C):
+    """THE shapes the pixel form runs at under ss2d_core = 'pixel': every shape its entry points accept (DESIGN.md section 24 has the per-stage
+    measurement); the others keep the composition, in the forward and the backward alike."""
+    return 1 <= C <= 1024 and B <= 65535 and B * H * W * 4 * C < 2 ** 31
+
+
+def _bc_view(xd, R):
+    """The B / C entries of the x_proj rows xd (M, 4 (R + 2)) as the (M, 4, 2) view the kernels read in place."""
+    M = xd.shape[0]
+    assert xd.is_contiguous() and xd.shape[1] % 4 == 0 and xd.shape[1] // 4 == R + 2
+    return xd.view(M, 4, R + 2)[:, :, R:]
+
+
+def _ss2d_core_fwd(u, dtp, xd, R, A, Ds, dt_bias, dims, chunk, stream):
+    """-> (ym (M, C), ws): the forward launch; ws holds what the backward needs of it and goes to _ss2d_core_bwd untouched."""
+    B, H, W = dims
+    M, C = u.shape
+    bc = _bc_view(xd, R)
+    ws = _ws(u.device, "ss2d_train", B, H, W, C, int(chunk))
+    ym = _f32((M, C), u.device)
+    _launch("xp_ss2d_train_fwd", u, stream, ptr(u), ptr(dtp), _vp(xd, R), int(bc.stride(0)), int(bc.stride(1)), ptr(A), ptr(Ds), ptr(dt_bias), ptr(ym),
+            ptr(ws), ctypes.c_size_t(ws.numel()), B, H, W, C, 1, int(chunk))
+    return ym, ws
+
+
+def _ss2d_core_bwd(dym, u, dtp, xd, R, A, Ds, dt_bias, ws, dims, chunk, stream):
+    """-> (du (M, C), ddtp (M, 4 C), dbc (M, 4, 2), dA, dD, ddt_bias (4, C) each): the backward launch on the forward's inputs and workspace."""
+    B, H, W = dims
+    M, C = u.shape
+    bc = _bc_view(xd, R)
+    dev = u.device
+    du, ddtp, dbc = _f32((M, C), dev), _f32((M, 4 * C), dev), _f32((M, 4, 2), dev)
+    dA, dD, ddb = _f32((4, C), dev), _f32((4, C), dev), _f32((4, C), dev)
+    _launch("xp_ss2d_train_bwd", u, stream, ptr(u), ptr(dtp), _vp(xd, R), int(bc.stride(0)), int(bc.stride(1)), ptr(A), ptr(Ds), ptr(dt_bias), ptr(dym),
+            ptr(du), ptr(ddtp), ptr(dbc), ptr(dA), ptr(dD), ptr(ddb), ptr(ws), ctypes.c_size_t(ws.numel()), B, H, W, C, 1, int(chunk))
+    return du, ddtp, dbc, dA, dD, ddb
+
+
+class _Ss2dCoreFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, dtp, xd, A, Ds, dt_bias, R, dims, chunk, stream):
+        ym, ws = _ss2d_core_fwd(u, dtp, xd, R, A, Ds, dt_bias, dims, chunk, stream)
+        ctx.args = (R, dims, chunk, stream)
+        ctx.save_for_backward(u, dtp, xd, A, Ds, dt_bias, ws)
+        return ym
+
+    @staticmethod
+    def backward(ctx, dym):
+        u, dtp, xd, A, Ds, dt_bias, ws = ctx.saved_tensors
+        R, dims, chunk, stream = ctx.args
+        du, ddtp, dbc, dA, dD, ddb = _ss2d_core_bwd(dym.contiguous(), u, dtp, xd, R, A, Ds, dt_bias, ws, dims, chunk, stream)
+        dxd = torch.zeros_like(xd)
+        _bc_view(dxd, R).copy_(dbc)
+        return du, ddtp.view(dtp.shape), dxd, dA.view(A.shape), dD.view(Ds.shape), ddb.view(dt_bias.shape), None, None, None, None
+
+
+def ss2d_core(u, dtp, xd, R, A, Ds, dt_bias, dims, chunk=0, stream=None):
+    """The SS2D core of a VSS block in pixel layout, one operator (csrc/train_ss2d.hip): cross-scan, the four-route selective scan (d_state 1) and
+    cross-merge without a (B, 4, C, L) tensor.  dims = (B, H, W), M = B H W: u (M, C); dtp (M, 4 C) or (M, 4, C), the dt projection before bias and
+    softplus; xd (M, 4 (R + 2)) the x_proj rows, whose B / C entries (columns R and R + 1 of each route's block) are read in place; A = -exp(A_logs),
+    Ds, dt_bias: 4 C elements each, route-major -> ym (M, C).  Differentiable in u, dtp, the B / C entries of xd (the gradient of its dt entries is
+    zero: they reach the core through dtp), A, Ds and dt_bias; the backward is the library's kernel only.  chunk: 0 (the library's choice) or a
+    power of two in [2, 64] with chunk C <= 6144."""
+    _check_operands("ss2d_core", u, dtp, xd, A, Ds, dt_bias)
+    B, H, W = (int(v) for v in dims)
+    R = int(R)
+    if u.dim() != 2 or min(B, H, W) < 1 or u.shape[0] != B * H * W:
+        raise ValueError(f"ss2d_core: u must be (B H W, C) of dims {tuple(dims)}, got {tuple(u.shape)}")
+    M, C = u.shape
+    if R < 0 or tuple(xd.shape) != (M, 4 * (R + 2)) or dtp.numel() != M * 4 * C or dtp.shape[0] != M:
+        raise ValueError(f"ss2d_core: dtp must be ({M}, {4 * C}) and xd ({M}, {4 * (R + 2)}); got {tuple(dtp.shape)}, {tuple(xd.shape)}")
+    if A.numel() != 4 * C or Ds.numel() != 4 * C or dt_bias.numel() != 4 * C:
+        raise ValueError(f"ss2d_core: A, Ds and dt_bias must hold 4 C = {4 * C} elements")
+    if not int(getattr(_lib.load(), "xp_ss2d_train_workspace_bytes")(B, H, W, C, int(chunk))):
+        raise ValueError(f"ss2d_core: dims {(B, H, W)}, C = {C}, chunk = {chunk}: batch <= 65535, C <= 1024, B H W 4 C < 2^31, and chunk 0 or a power "
+                         "of two in [2, 64] with chunk C <= 6144")
+    with torch.cuda.device(u.device):
+        return _Ss2dCoreFn.apply(u.contiguous(), dtp.contiguous(), xd.contiguous(), A.contiguous(), Ds.contiguous(), dt_bias.contiguous(), R, (B, H, W),
+                                 int(chunk), stream)
 
 
 # ---- the forward engine as the autograd functions launch it (no checks; the caller passes its stream down)

@@ -1,6 +1,7 @@
 """One block of the VMamba encoder (reference xpoint/models/vmamba_src/VMamba.py:1153-1234) as a trainable module (csrc/train_vss.hip, DESIGN.md
 section 16): LayerNorm, in_proj, depthwise conv + SiLU, x_proj, the dt projection, the SS2D core composed from the differentiable cross-scan /
-selective-scan / cross-merge operators, out_norm, out_proj and the MLP, with stochastic depth.  Its backward is HIP only and passes the gradient
+selective-scan / cross-merge operators — or, with `ss2d_core = "pixel"` (set_ss2d_core), one operator in pixel layout that keeps no route tensor
+(csrc/train_ss2d.hip) — out_norm, out_proj and the MLP, with stochastic depth.  Its backward is HIP only and passes the gradient
 through to its input, so blocks stack.  Every linear layer takes its input gradient by `_linear_dgrad` (the forward engine on the transposed weight).
 Patch embed, the downsamplers and the stacking of the blocks are encoder.py's (VSSEncoder)."""
 import math
@@ -9,8 +10,8 @@ import torch
 
 from .. import _lib
 from .._lib import ptr
-from .ops import (TrainModule, _layernorm, _linear, _linear_dgrad, _need_device, add_scaled_rows, colsum_rows, dwconv3x3_silu_bwd, gelu_bwd, gelu_fwd,
-                  gemm_tn, layernorm_bwd, scale_grad)
+from .ops import (TrainModule, _layernorm, _linear, _linear_dgrad, _need_device, _ss2d_core_bwd, _ss2d_core_fwd, add_scaled_rows, check_ss2d_core,
+                  colsum_rows, dwconv3x3_silu_bwd, gelu_bwd, gelu_fwd, gemm_tn, layernorm_bwd, scale_grad, ss2d_takes_pixel)
 
 
 def _dt_block_diagonal(dt_w, R2):
@@ -39,13 +40,45 @@ def _branch_bwd_close(dt, x, norm_w, dy, B, want_dx, st):
     return add_scaled_rows(dy.view(B, -1, C), dx.view(B, -1, C), ones, stream=st).view(-1, C), dn_w, dn_b
 
 
+def _core_routes_fwd(t3, dtp, xd, R, A, Ds, dt_b, dims):
+    """The SS2D core as the composition of the operator-level kernels: three cross-scans into (B, 4, C, L) route tensors, the selective scan, the
+    cross-merge -> (ym (M, C), what _core_routes_bwd needs)."""
+    from ..kernels import _cross_merge, _cross_scan, _selective_scan_fn_nograd
+    B, H, W = dims
+    M, C = t3.shape
+    R2, L = R + 2, H * W
+    xs = _cross_scan(t3.view(B, H, W, C), False, True, False, 0)                   # (B, 4, C, L)
+    dts = _cross_scan(dtp.view(B, H, W, 4, C), False, True, True, 0)               # one_by_one, channel-last in: (B, 4, C, L)
+    bc = _cross_scan(xd.view(M, 4, R2)[:, :, R:].reshape(B, H, W, 4, 2), False, True, True, 0)      # (B, 4, 2, L): B and C (d_state 1)
+    Bs, Cs = bc[:, :, 0:1].contiguous(), bc[:, :, 1:2].contiguous()
+    ys, xstate = _selective_scan_fn_nograd(xs.view(B, 4 * C, L), dts.view(B, 4 * C, L), A, Bs, Cs, Ds.detach(), dt_b.detach().reshape(-1), True, want_x=True)
+    ym = _cross_merge(ys.view(B, 4, C, H, W), False, True, False, 0).view(M, C)
+    return ym, (xs, dts, Bs, Cs, xstate)
+
+
+def _core_routes_bwd(dym, kept, A, Ds, dt_b, dims):
+    """dym (M, C) -> (du (M, C), ddtp (M, 4 C), dbc (M, 4, 2), dA, dD, ddt_bias): the adjoints of _core_routes_fwd's launches."""
+    from ..kernels import _cross_merge, _cross_scan, selective_scan_bwd
+    xs, dts, Bs, Cs, xstate = kept
+    B, H, W = dims
+    M, C = dym.shape
+    L = H * W
+    dys = _cross_scan(dym.view(B, H, W, C), False, True, False, 0)                 # the merge's adjoint: (B, 4, C, L)
+    du, ddelta, dA, dB, dC, dD, ddb = selective_scan_bwd(xs.view(B, 4 * C, L), dts.view(B, 4 * C, L), A, Bs, Cs, Ds, dt_b.reshape(-1),
+                                                         dys.view(B, 4 * C, L), xstate, True, 1)
+    dt3 = _cross_merge(du.view(B, 4, C, H, W), False, True, False, 0).view(M, C)   # the scan's adjoint
+    ddtp = _cross_merge(ddelta.view(B, 4, C, H, W), False, True, True, 0).view(M, 4 * C)
+    dbc = _cross_merge(torch.cat([dB, dC], 2).view(B, 4, 2, H, W), False, True, True, 0).view(M, 4, 2)
+    return dt3, ddtp, dbc, dA, dD, ddb
+
+
 class _SsmBranchFn(torch.autograd.Function):
     """x (M, C) rows of (B, H, W) -> x + s[b] out_proj(out_norm(SS2D(silu(dwconv(in_proj(LN(x))))))); s None: no factor, the residual rides in the
-    out_proj launch.  Parameters in the reference's order."""
+    out_proj launch.  Parameters in the reference's order.  core: the form of the SS2D core between dtp and ym, 'routes' (_core_routes_fwd / _bwd) or
+    'pixel' (ops.ss2d_core's launches, at the shapes ss2d_takes_pixel names)."""
 
     @staticmethod
-    def forward(ctx, x, s, dims, norm_w, norm_b, xproj_w, A_logs, Ds, dt_w, dt_b, on_w, on_b, in_w, conv_w, out_w):
-        from ..kernels import _cross_merge, _cross_scan, _selective_scan_fn_nograd
+    def forward(ctx, x, s, dims, norm_w, norm_b, xproj_w, A_logs, Ds, dt_w, dt_b, on_w, on_b, in_w, conv_w, out_w, core="routes"):
         B, H, W = dims
         M, C = x.shape
         R = dt_w.shape[2]
@@ -59,43 +92,42 @@ class _SsmBranchFn(torch.autograd.Function):
         xd = _linear(t3, xproj_w.reshape(4 * R2, C), st)                              # x_proj in pixel layout: (M, 4 (R + 2))
         wbd = _dt_block_diagonal(dt_w, R2)
         dtp = _linear(xd, wbd, st)                                                     # (M, 4 C): every direction's dt at its pixel
-        xs = _cross_scan(t3.view(B, H, W, C), False, True, False, 0)                   # (B, 4, C, L)
-        dts = _cross_scan(dtp.view(B, H, W, 4, C), False, True, True, 0)               # one_by_one, channel-last in: (B, 4, C, L)
-        bc = _cross_scan(xd.view(M, 4, R2)[:, :, R:].reshape(B, H, W, 4, 2), False, True, True, 0)      # (B, 4, 2, L): B and C (d_state 1)
-        Bs, Cs = bc[:, :, 0:1].contiguous(), bc[:, :, 1:2].contiguous()
         A = -torch.exp(A_logs.detach().float())
-        ys, xstate = _selective_scan_fn_nograd(xs.view(B, 4 * C, L), dts.view(B, 4 * C, L), A, Bs, Cs, Ds.detach(), dt_b.detach().reshape(-1), True, want_x=True)
-        ym = _cross_merge(ys.view(B, 4, C, H, W), False, True, False, 0).view(M, C)
+        pixel = check_ss2d_core(core, "VSSBlock") == "pixel" and ss2d_takes_pixel(B, H, W, C)
+        if pixel:
+            ym, ws = _ss2d_core_fwd(t3, dtp, xd, R, A, Ds.detach(), dt_b.detach(), dims, 0, st)
+            kept = (ws,)          # the chunk states; dtp, a route tensor's size, is not kept: the backward repeats its GEMM (the same bits)
+        else:
+            ym, kept = _core_routes_fwd(t3, dtp, xd, R, A, Ds, dt_b, dims)
         yn = _layernorm(ym, on_w, on_b, st)
         if s is None:
             out = _linear(yn, out_w, st, res=x)
         else:
             out = add_scaled_rows(x.view(B, L, C), _linear(yn, out_w, st).view(B, L, C), s, stream=st).view(M, C)
-        ctx.dims, ctx.has_s = dims, s is not None
-        ctx.save_for_backward(x, t1, t2, t3, xd, xs, dts, Bs, Cs, A, xstate, ym, yn, w9c, wbd, norm_w, xproj_w, Ds, dt_w, dt_b, on_w, in_w, out_w,
+        ctx.dims, ctx.has_s, ctx.pixel = dims, s is not None, pixel          # the backward takes the form the forward took
+        ctx.save_for_backward(x, t1, t2, t3, xd, A, ym, yn, w9c, wbd, norm_w, xproj_w, Ds, dt_w, dt_b, on_w, in_w, out_w, *kept,
                               *(() if s is None else (s,)))
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        from ..kernels import _cross_merge, _cross_scan, selective_scan_bwd
-        x, t1, t2, t3, xd, xs, dts, Bs, Cs, A, xstate, ym, yn, w9c, wbd, norm_w, xproj_w, Ds, dt_w, dt_b, on_w, in_w, out_w = ctx.saved_tensors[:23]
+        saved = ctx.saved_tensors
+        x, t1, t2, t3, xd, A, ym, yn, w9c, wbd, norm_w, xproj_w, Ds, dt_w, dt_b, on_w, in_w, out_w = saved[:18]
+        kept = saved[18:len(saved) - ctx.has_s]
         B, H, W = ctx.dims
         M, C = x.shape
         R = dt_w.shape[2]
         R2, L = R + 2, H * W
         st = _lib.current_stream(x)
         dy = dy.contiguous()
-        gs, sc = _branch_bwd_open(dy, ctx.saved_tensors[23] if ctx.has_s else None, B, st)
+        gs, sc = _branch_bwd_open(dy, saved[-1] if ctx.has_s else None, B, st)
         d_out_w = gemm_tn(gs, yn, p_scale=sc, stream=st)
         dyn = _linear_dgrad(gs, sc, out_w, st)
         dym, d_on_w, d_on_b, _ = layernorm_bwd(dyn, ym, on_w, stream=st)
-        dys = _cross_scan(dym.view(B, H, W, C), False, True, False, 0)                 # the merge's adjoint: (B, 4, C, L)
-        du, ddelta, dA, dB, dC, dD, ddb = selective_scan_bwd(xs.view(B, 4 * C, L), dts.view(B, 4 * C, L), A, Bs, Cs, Ds, dt_b.reshape(-1),
-                                                             dys.view(B, 4 * C, L), xstate, True, 1)
-        dt3 = _cross_merge(du.view(B, 4, C, H, W), False, True, False, 0).view(M, C)   # the scan's adjoint
-        ddtp = _cross_merge(ddelta.view(B, 4, C, H, W), False, True, True, 0).view(M, 4 * C)
-        dbc = _cross_merge(torch.cat([dB, dC], 2).view(B, 4, 2, H, W), False, True, True, 0).view(M, 4, 2)
+        if ctx.pixel:
+            dt3, ddtp, dbc, dA, dD, ddb = _ss2d_core_bwd(dym, t3, _linear(xd, wbd, st), xd, R, A, Ds, dt_b, kept[0], ctx.dims, 0, st)
+        else:
+            dt3, ddtp, dbc, dA, dD, ddb = _core_routes_bwd(dym, kept, A, Ds, dt_b, ctx.dims)
         # the dt projection: one block-diagonal GEMM over the whole x_proj row; its weight gradient is the diagonal blocks of one gemm_tn result
         g2, sc2 = scale_grad(ddtp, out=ddtp, stream=st)
         d_wbd = gemm_tn(g2, xd, p_scale=sc2, stream=st).view(4, C, 4, R2)
@@ -113,7 +145,8 @@ class _SsmBranchFn(torch.autograd.Function):
         dt1 = _linear_dgrad(dt2, sc4, in_w, st)
         dx, d_norm_w, d_norm_b = _branch_bwd_close(dt1, x, norm_w, dy, B, ctx.needs_input_grad[0], st)
         # A = -exp(A_logs): dA_logs = dA A (parameter-sized)
-        return dx, None, None, d_norm_w, d_norm_b, d_xproj, (dA * A).view(4 * C, 1), dD, d_dt_w, ddb.view(4, C), d_on_w, d_on_b, d_in_w, d_conv_w, d_out_w
+        return (dx, None, None, d_norm_w, d_norm_b, d_xproj, (dA.view(A.shape) * A).view(4 * C, 1), dD.view(Ds.shape), d_dt_w, ddb.view(4, C), d_on_w, d_on_b, d_in_w,
+                d_conv_w, d_out_w, None)
 
 
 class _MlpBranchFn(torch.autograd.Function):
@@ -201,6 +234,7 @@ class VSSBlock(TrainModule):
         if encoder not in ("encoder.", "encoder_thermal.", "encoder_optical."):
             raise ValueError(f"VSSBlock: encoder must be 'encoder.', 'encoder_thermal.' or 'encoder_optical.' (got {encoder!r})")
         self.prefix = f"{encoder}layers.{int(stage)}.blocks.{int(block)}."
+        self.ss2d_core = "routes"          # the form of the SS2D core in training: 'routes' or 'pixel' (set_ss2d_core)
         nn = torch.nn
         blk = nn.Module()          # parameter containers with the reference's names, order and initialisation; forward() never calls them
         blk.norm = nn.LayerNorm(C)
@@ -273,7 +307,22 @@ class VSSBlock(TrainModule):
         with torch.cuda.device(dev):
             x = _SsmBranchFn.apply(x, s1, (B, H, W), t("norm.weight"), t("norm.bias"), t("op.x_proj_weight"), t("op.A_logs"), t("op.Ds"),
                                    t("op.dt_projs_weight"), t("op.dt_projs_bias"), t("op.out_norm.weight"), t("op.out_norm.bias"),
-                                   t("op.in_proj.weight"), t("op.conv2d.weight"), t("op.out_proj.weight"))
+                                   t("op.in_proj.weight"), t("op.conv2d.weight"), t("op.out_proj.weight"), self.ss2d_core if self.training else "routes")
             x = _MlpBranchFn.apply(x, s2, B, t("norm2.weight"), t("norm2.bias"), t("mlp.fc1.weight"), t("mlp.fc1.bias"), t("mlp.fc2.weight"),
                                    t("mlp.fc2.bias"))
         return x.view(B, H, W, C)
+
+
+def set_ss2d_core(module, kind):
+    """Chooses the form of the SS2D core for every VSS block under `module` (a VSSBlock, VSSEncoder or XPointNet): 'routes', the default — the
+    cross-scan / selective-scan / cross-merge composition over (B, 4, C, L) route tensors — or 'pixel', the one operator in pixel layout
+    (ops.ss2d_core), which keeps no route tensor.  The two agree to rounding, not bit for bit.  `.eval()` forwards are the same under both.  Returns
+    the module."""
+    check_ss2d_core(kind, "set_ss2d_core")
+    # the attribute lives on VSSBlock and on VSSEncoder (which runs its blocks itself); XPointNet keeps its encoders in `_encoders`, outside its children
+    holders = [h for m in module.modules() for h in (m, *getattr(m, "_encoders", {}).values()) if isinstance(getattr(h, "ss2d_core", None), str)]
+    for h in holders:
+        h.ss2d_core = kind
+    if not holders:
+        raise ValueError(f"set_ss2d_core: {type(module).__name__} holds no VSS block")
+    return module
