@@ -1,4 +1,4 @@
-"""Which path of csrc/postproc.hip a shape takes, pinned without a GPU.
+"""Which path of csrc/box_nms.hip a shape takes, pinned without a GPU.
 
 `xp_box_nms_plan` answers with the launcher's own functions (make_nms_table, nms_two_launch_applies, nms_finish_plan), so these tests read the
 library, not a copy of its rules.  tests/test_gpu_postproc_paths.py relies on every plan asserted here: a later change of a tile size, of the LDS
@@ -96,6 +96,26 @@ def test_ridges_outrank_their_fields():
         assert p[sl].min() >= 0.5 and p[0][~r[0]].max() < 0.5
         vals, counts = np.unique(p[0][~r[0]], return_counts=True)
         assert counts.min() > 1 and len(vals) <= 256
+
+
+# (batch, H, W, cap) -> xp_box_nms_workspace_bytes, xp_extract_keypoints_workspace_bytes(batch, H, W): recorded from the library as it was before
+# box NMS and keypoint extraction moved into files of their own, never computed by the code under test
+WORKSPACE_BYTES = [
+    ((1, 1, 32, 1), 2080, 260),
+    ((2, 65, 33, 1), 40272, 280),
+    ((2, 200, 24, 1), 88128, 296),                   # the sweep form
+    ((3, 96, 256, 24576), 1550176, 544),
+    ((2, 181, 2048, 1), 6677056, 3152),
+    ((16, 480, 640, 8192), 45833216, 19456),
+]
+
+
+def test_workspace_sizes_are_the_recorded_ones(lib):
+    """The workspace layout has one definition (nms_core.h: nms_ws_layout); callers size their buffers with these two queries and tools/nms_bench.py
+    reads the finisher's diagnostics from the END of the NMS workspace, so the totals may not move."""
+    for shape, nms_bytes, kp_bytes in WORKSPACE_BYTES:
+        assert lib.xp_box_nms_workspace_bytes(*shape) == nms_bytes, shape
+        assert lib.xp_extract_keypoints_workspace_bytes(*shape[:3]) == kp_bytes, shape
 
 
 def test_plan_refuses_what_the_launcher_refuses(lib):

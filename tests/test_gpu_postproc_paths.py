@@ -1,4 +1,4 @@
-"""Every path of csrc/postproc.hip against the oracle: both forms of box NMS (tile sweeps; local maxima + finisher, every reach, bands, the
+"""Every path of csrc/box_nms.hip and csrc/keypoints.hip against the oracle: both forms of box NMS (tile sweeps; local maxima + finisher, every reach, bands, the
 undecided list in LDS and in the workspace, the stream-ordered modes), both paths of keypoint extraction and both of descriptor sampling.
 
 Which path a shape takes is not assumed here: tests/test_cpu_postproc_plan.py pins it with `xp_box_nms_plan`, and the tests below assert the plan

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 T=/tmp/nmsdbg; rm -rf $T; mkdir -p $T; cp -r $R/xpoint_amd $R/include $R/tools $T/; cd $T
 for m in ${1:-0 1 2 4 8}; do
-  hipcc -x hip -c xpoint_amd/csrc/postproc.hip -o xpoint_amd/csrc/_obj/postproc.hip.o --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I include -I xpoint_amd/csrc -DXP_NMS_DBG=$m 2>/dev/null
+  hipcc -x hip -c xpoint_amd/csrc/box_nms.hip -o xpoint_amd/csrc/_obj/box_nms.hip.o --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I include -I xpoint_amd/csrc -DXP_NMS_DBG=$m 2>/dev/null
   hipcc -shared -fPIC --offload-arch=gfx950 -o xpoint_amd/libxpoint_hip.so xpoint_amd/csrc/_obj/*.o
   echo "== XP_NMS_DBG=$m (1 no candidate tests, 2 no out store, 4 no list building, 8 no loads, 16 no window walk)"
   cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/nst

@@ -61,7 +61,7 @@ __device__ __forceinline__ unsigned long long pack_key(float d2, int idx) {
 __device__ __forceinline__ float mt_max(float a, float b) { float d; asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ float mt_max3(float a, float b, float c) { float d; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 
-// (a kernel, not hipMemsetAsync: see nms_reset_counters_kernel in postproc.hip)
+// (a kernel, not hipMemsetAsync: see nms_reset_counters_kernel in box_nms.hip)
 __global__ void match_reset_kernel(unsigned* __restrict__ maxbits) { if (threadIdx.x < 8) maxbits[threadIdx.x] = 0u; }
 
 // ---- pass 0a: squared norms of both descriptor sets and the largest one of the call ----

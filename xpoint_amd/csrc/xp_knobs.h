@@ -43,9 +43,8 @@ static const XpKnob kXpKnobs[] = {
     {"XP_SCAN_V2", "selective_scan.hip", "force the second d_state = 1 operator-boundary scan kernel"},
     {"XP_SCAN_OLD_GEN", "selective_scan.hip", "1: the round-1 generic-N operator-boundary scan kernel"},
     // ---- glue / post-processing
-    {"XP_NMS_SCHED", "postproc.hip", "NMS local-iteration schedule"},
-    {"XP_NMS_SWEEP", "postproc.hip", "NMS sweep count"},
-    {"XP_NMS_WIDE_ROUNDS", "postproc.hip", "wide suppression rounds ahead of the NMS finisher"},
+    {"XP_NMS_SCHED", "box_nms.hip", "NMS local-iteration schedule"},
+    {"XP_NMS_SWEEP", "box_nms.hip", "NMS sweep count"},
     // ---- profiling
     {"XP_PROF_SHAPES", "api.cpp", "1: per-shape tags in the HIP-event breakdown (xp_prof_*)"},
     // ---- host side (Python)
