@@ -530,6 +530,38 @@ int xp_find_homography(const float* src, const float* dst, const int* counts, in
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Matching evaluation for a batch of pairs (csrc/pair_eval.hip; DESIGN.md "Matching evaluation"): the device work of
+ * benchmark_evaluation.py's compute_repeatability_for_sample (:396-467), compute_descriptor_for_sample (:588-751) and the corner error
+ * of compute_pts_dist_for_sample (:755-830) on ragged batches.  kp (2*pairs, cap, 2) int32 (y, x), optical images first; counts
+ * (2*pairs) int32 (a count above cap means a truncated list: min(count, cap) rows are used); the match lists are xp_match_mnn's.
+ * Image i < pairs is the optical image of pair i and image pairs + i its thermal image; "the other image" of i is (i + pairs) % (2 pairs).
+ * Every quantity of pair p is what the pair gives alone; no float atomics; rows at or beyond a count are never read as data.
+ *
+ * xp_pair_eval_warp_near: every keypoint of image i through map1[i] and, when map2 != NULL, then map2[i] (both (2*pairs, 9) f64 row-major, acting
+ *   on (x, y, 1)): hom = (x*h0 + y*h1) + h2 ..., divided by the third coordinate, in f64 without contraction (homographies.py:479-497).
+ *   truncate != 0: each map is followed by numpy's astype(int) (toward zero; non-finite or beyond int64 gives INT64_MIN) — repeatability.
+ *   warped (2*pairs, cap, 2) f64 (y, x); inframe (2*pairs, cap) u8 = filter_points (homographies.py:511-526) on an H x W frame;
+ *   near (2*pairs, cap) f32 = min over the other image's keypoints of the norm (difference in f64, cast to f32, dx*dx + dy*dy and sqrt in f32;
+ *   xp_points_min_dist's arithmetic), +inf when the other image has none.  Filler rows: warped 0, inframe 0, near +inf.
+ * xp_pair_eval_match_dist: for match j of pair p (q = match_q, t = match_t): dist (2, pairs, cap) f32, [0] = |warped[p][q] - kp[pairs + p][t]|,
+ *   [1] = |warped[pairs + p][t] - kp[p][q]| (f64 difference cast to f32, sqrt(dx*dx + dy*dy) in f32: the entries of the correct-match matrix the match loop reads, benchmark_evaluation.py:655-675).
+ *   Filler (j >= match_count, or an index outside its list): +inf.
+ * xp_pair_eval_count: thresholds (T <= 16) are HOST floats passed by value.  near_cnt (2, pairs, T) = rows of image (dir * pairs + p) with
+ *   near <= th, over the rows below the count (near_inframe_only == 0) or those of them that are in frame (!= 0: repeatability counts the
+ *   filtered points only); match_cnt (2, pairs, T) = matches with dist <= th (0 when dist == NULL); n_inframe (2, pairs).  Integer sums.
+ * xp_pair_eval_corner_error: err (pairs) f64 = mean over the reference's point list [[0,0],[H,0],[0,W],[H,H]] (as (y, x), kept as it is) of
+ *   |warp(H_est) - warp(H_gt)| in f64; 999.0 where n_inliers == 0 or match_count < 4.  H_gt, H_est (pairs, 9) f64 on the device. */
+int xp_pair_eval_warp_near(const int* kp, const int* counts, int pairs, int cap, int H, int W, const double* map1, const double* map2,
+                           int truncate, double* warped, uint8_t* inframe, float* near_dist, void* stream);
+int xp_pair_eval_match_dist(const int* kp, const int* counts, const double* warped, const int* match_q, const int* match_t,
+                            const int* match_count, int pairs, int cap, float* dist, void* stream);
+int xp_pair_eval_count(const float* near_dist, const uint8_t* inframe, const int* counts, const float* dist, const int* match_count, int pairs,
+                       int cap, const float* thresholds_host, int T, int near_inframe_only, int* near_cnt, int* match_cnt, int* n_inframe,
+                       void* stream);
+int xp_pair_eval_corner_error(const double* H_gt, const double* H_est, const int* n_inliers, const int* match_count, int pairs, int H, int W,
+                              double* err, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Perspective warp — the reference's registration output:
  *     cv2.warpPerspective(im_optical, H_est, im_optical.shape[:2][::-1], borderMode=cv2.BORDER_CONSTANT)
  * (predict_align_image_pair.py:308, demo.py:225-249): INTER_LINEAR, border value 0, M (batch, 9) f64 ON THE DEVICE = the forward

@@ -1,0 +1,159 @@
+"""CPU: the batched matching evaluation (DESIGN.md "Matching evaluation") without a GPU — the numpy restatement of the xp_pair_eval_* kernels
+(tests/pair_eval_cases.py) against the REAL reference's repeatability numbers (tests/golden/g13_eval_metrics.npz, produced by the reference's
+benchmark_evaluation.py on synth.make_eval_case), the exported and declared symbols, and the configuration handling of `fit` and
+`cli benchmark`."""
+import numpy as np
+import pytest
+import torch
+
+from tests import pair_eval_cases as pc
+from xpoint_amd import synth
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_restated_repeatability_reproduces_the_reference(golden, seed):
+    """warp_near (two truncating maps, in-frame flag, nearest distance) + count on the keypoints of make_eval_case give the reference's
+    keypoint counts exactly and its repeatability (the LAST sample's entry: the reference overwrites it per sample) to 1e-12."""
+    from xpoint_amd import evaluation as ev
+    g = golden("g13_eval_metrics.npz")
+    c = synth.make_eval_case(seed)
+    B, _, H, W = c["prob_optical"].shape
+    kp, counts, cap = pc.eval_case_keypoints(c)
+    assert counts[:B].tolist() == g[f"s{seed}/rep/n_kp_optical"].tolist() and counts[B:].tolist() == g[f"s{seed}/rep/n_kp_thermal"].tolist()
+    m1, m2, _, _ = ev.pair_eval_matrices(torch.from_numpy(c["H_optical"]), torch.from_numpy(c["H_thermal"]))
+    cnt, n = pc.repeatability(kp, counts, B, cap, H, W, m1, m2, [1, 3, 5])
+    assert n[B - 1] > 0
+    for k, th in enumerate((1, 3, 5)):
+        ref = g[f"s{seed}/rep/{th}"]
+        assert ref.shape == (1,) and abs(cnt[B - 1, k] / n[B - 1] - ref[0]) <= 1e-12, (th, cnt[B - 1, k], n[B - 1], ref)
+    # the numerator is an integer: with the denominator known, the ratio pins it
+    assert [int(round(float(g[f"s{seed}/rep/{th}"][0]) * n[B - 1])) for th in (1, 3, 5)] == cnt[B - 1].tolist()
+
+
+def test_restatement_matches_the_module_arithmetic():
+    """warp / trunc_int against evaluation.warp_keypoints (a BLAS product: equal up to the last bit of float64, equal after astype(int) on these
+    points) and filter_points; the nearest distance against the all-pairs formula of the reference."""
+    from xpoint_amd import evaluation as ev
+    case = pc.make_kernel_case("full")
+    P, cap, H, W = case["pairs"], case["cap"], case["H"], case["W"]
+    m1, m2 = case["maps"]["rep"]
+    warped, inframe, near = pc.warp_near(case["kp"], case["counts"], P, cap, H, W, m1, m2, True)
+    for img in range(2 * P):
+        n, m = int(case["counts"][img]), int(case["counts"][(img + P) % (2 * P)])
+        pts = ev.warp_keypoints(ev.warp_keypoints(case["kp"][img, :n], m1[img].reshape(3, 3)), m2[img].reshape(3, 3))
+        assert np.array_equal(warped[img, :n], pts.astype(np.float64))
+        kept = ev.filter_points(pts, (H, W))
+        assert int(inframe[img].sum()) == len(kept) and not inframe[img, n:].any() and not warped[img, n:].any()
+        diff = (pts[:, None, :].astype(np.float64) - case["kp"][(img + P) % (2 * P), :m].astype(np.float32)[None]).astype(np.float32)
+        ref = np.sqrt(diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]).min(1)
+        assert np.array_equal(near[img, :n], ref) and np.isinf(near[img, n:]).all()
+    v = np.array([0.0, -0.25, -1.0, 2.999, -2.999, np.nan, np.inf, -np.inf, 1e30, -1e30])
+    with np.errstate(all="ignore"):
+        assert np.array_equal(pc.trunc_int(v), v.astype(np.int64).astype(np.float64))
+    assert not np.signbit(pc.trunc_int(np.array([-0.25]))).any()
+
+
+def test_restated_counts_and_corner_error():
+    case = pc.make_kernel_case("ragged")
+    P, cap, H, W = case["pairs"], case["cap"], case["H"], case["W"]
+    m1, _ = case["maps"]["desc"]
+    warped, inframe, near = pc.warp_near(case["kp"], case["counts"], P, cap, H, W, m1, None, False)
+    assert np.isinf(near[P + 2, :0]).all() and np.isinf(near[2, 0])                      # the other image has no keypoint: +inf
+    assert inframe[0, :300].all() and not inframe[P + 1, :7].all()                      # identity keeps all; the inverse translation pushes points out
+    dist = pc.match_dist(case["kp"], case["counts"], warped, case["match_q"], case["match_t"], case["match_count"], P, cap)
+    assert np.isfinite(dist[:, 0, :120]).all() and np.isinf(dist[:, 0, 120:]).all() and np.isinf(dist[:, 1:]).all()
+    ths = pc.THRESHOLD_LISTS["T10"]
+    near_cnt, match_cnt, n_in = pc.count(near, inframe, case["counts"], dist, case["match_count"], P, cap, ths, False)
+    assert (np.diff(near_cnt, axis=2) >= 0).all() and (np.diff(match_cnt, axis=2) >= 0).all()
+    assert n_in[0, 0] == 300 and near_cnt[0, 2].tolist() == [0] * 10 and match_cnt[:, 1:].sum() == 0
+    # identity pair: integer differences, so th = 1 counts the exact ties |d| == 1
+    d0 = near[0, :300]
+    assert ((d0 == 1.0).sum() > 0) and near_cnt[0, 0, 0] == (d0 <= 1.0).sum()
+    gt, est, n_inl, mc, Hc, Wc = pc.make_corner_case()
+    err = pc.corner_error(gt, est, n_inl, mc, 4, Hc, Wc)
+    assert err[1] == 999.0 and err[2] == 999.0 and 0 < err[0] < 1 and 0 < err[3] < 1
+    from xpoint_amd import evaluation as ev
+    pts = np.array([[0, 0], [Hc, 0], [0, Wc], [Hc, Hc]])
+    ref = np.linalg.norm(ev.warp_keypoints(pts, est[0].reshape(3, 3), float) - ev.warp_keypoints(pts, gt[0].reshape(3, 3), float), axis=1).sum() / 4
+    assert abs(err[0] - ref) <= 1e-12
+
+
+def test_new_symbols_are_exported_and_declared():
+    from xpoint_amd import _lib, evaluation as ev, cli
+    from xpoint_amd.training.fit import validation_metric_thresholds      # noqa: F401
+    names = ["xp_pair_eval_warp_near", "xp_pair_eval_match_dist", "xp_pair_eval_count", "xp_pair_eval_corner_error"]
+    declared = _lib.exported_symbols()
+    for n in names:
+        assert n in declared and n in _lib._SIGNATURES, n
+    for n in ("pair_metrics_batched", "compute_metrics_batched", "pair_eval_matrices", "download_pair_metrics", "repeatability_from_batch",
+              "descriptor_from_batch"):
+        assert callable(getattr(ev, n)), n
+    assert callable(cli.benchmark) and callable(cli.benchmark_results)
+    import inspect
+    sig = list(inspect.signature(ev.pair_metrics_batched).parameters)
+    assert sig[:13] == ["prob_rep_o", "prob_rep_t", "prob_desc_o", "prob_desc_t", "desc_o", "desc_t", "H_o", "H_t", "detection_threshold",
+                        "thresh_repeatability", "thresh_keypoints", "ransac_reproj_thresholds", "cap"]
+    a, b = inspect.signature(ev.compute_metrics_batched).parameters, inspect.signature(ev.compute_metrics).parameters
+    assert list(a)[:len(b)] == list(b) and [a[k].default for k in b] == [b[k].default for k in b] and a["reference_quirks"].default is True
+
+
+def test_fit_metric_configuration():
+    from xpoint_amd.training.fit import validation_metric_thresholds as vmt
+    assert vmt(None) is None and vmt({}) is None
+    assert vmt({"compute_validation_loss": True, "foldername": "v"}) is None                                  # no key: nothing is read
+    assert vmt({"compute_validation_loss": False, "compute_metrics": True}) is None                           # read only with a validation folder in use
+    assert vmt({"compute_validation_loss": True, "foldername": "v", "compute_metrics": True}) == [3]
+    assert vmt({"compute_validation_loss": True, "foldername": "v", "compute_metrics": True, "metric_thresholds": [1, 2.5]}) == [1, 2.5]
+    with pytest.raises(ValueError, match="foldername"):
+        vmt({"compute_validation_loss": True, "compute_metrics": True})
+    for bad in ([], [0], [-1], ["3"], 3, [3, 3], [True], list(range(1, 18)), [float("nan")]):
+        with pytest.raises(ValueError, match="metric_thresholds"):
+            vmt({"compute_validation_loss": True, "foldername": "v", "compute_metrics": True, "metric_thresholds": bad})
+
+
+def test_cli_benchmark_arguments_and_result_keys():
+    from xpoint_amd import cli
+    args = cli.build_parser().parse_args(["benchmark", "-y", "c.yaml", "-m", "weights/XPoint-EXP1", "-v", "e20", "-o", "out.json"])
+    assert (args.flow, args.yaml_config, args.model_dir, args.version, args.output, args.seed) == ("benchmark", "c.yaml", "weights/XPoint-EXP1", "e20",
+                                                                                                     "out.json", 0)
+    with pytest.raises(SystemExit):
+        cli.build_parser().parse_args(["benchmarks"])
+    assert cli.BENCHMARK_THRESHOLDS == list(range(1, 11)) and cli.BENCHMARK_RANSAC_THRESHOLDS == [2]
+    out = {"repeatability": {"repeatability_mean": {1: np.float64(0.5), 2: np.float64(0.75)}, "n_kp_optical": np.float64(10.0),
+                             "n_kp_thermal": np.float64(12.0), "n_kp_avg": 11.0},
+           "descriptor": {1: {"nn_map": np.float64(0.4), "m_score": np.float64(0.3), "tp_optical": np.zeros(3, bool)},
+                          2: {"nn_map": np.float64(0.6), "m_score": np.float64(0.5), "tp_optical": np.zeros(3, bool)}},
+           "homography": {2: {"average_h_error": np.float64(1.5), "h_correctness": {"epsilon_warp_th1": np.float64(0.25)}}}}
+    config = {"dataset": {"foldername": "data/pairs", "height": 480, "width": 640}, "prediction": {"nms": 4}}
+    res = cli.benchmark_results(out, config, "weights/XPoint-EXP1", "e20", 0.015)
+    import json
+    back = json.loads(json.dumps(res))
+    assert back == res
+    assert set(res) == {"repeatability", "descriptor", "homography", "model_dir", "model_version", "height-width", "dataset", "nms", "detection_th",
+                        "threshold_keypoints_for_descriptor", "threshold_homography_epsilon", "threshold_repeatability_distance_th",
+                        "ransac_reproj_thresholds"}
+    assert res["descriptor"] == {"th_kp_1": {"nn_map": 0.4, "m_score": 0.3}, "th_kp_2": {"nn_map": 0.6, "m_score": 0.5}}
+    assert res["repeatability"]["repeatability_mean"] == {"1": 0.5, "2": 0.75} and res["height-width"] == "480,640" and res["dataset"] == "data/pairs"
+    assert res["homography"]["2"]["h_correctness"]["epsilon_warp_th1"] == 0.25
+
+
+def test_batch_assembly_quirks():
+    """repeatability_from_batch / descriptor_from_batch on a hand-made downloaded batch: reference_quirks keeps the last sample's repeatability and
+    n_gt, without it every sample counts."""
+    from xpoint_amd import evaluation as ev
+    inf = np.float32(np.inf)
+    r = {"n_kp": np.array([5, 6, 7, 8], np.int32), "rep_count": np.array([[[2], [3]], [[1], [0]]], np.int32), "rep_inframe": np.array([[4, 0], [4, 0]], np.int32),
+         "match_count": np.array([2, 1], np.int32), "n_gt": np.array([[[3], [4]], [[5], [6]]], np.int32), "desc_inframe": np.array([[4, 0], [2, 5]], np.int32),
+         "match_ok": np.array([[[1], [1]], [[2], [0]]], np.int32),
+         "match_dist": np.array([[[0.1, 0.2, inf], [0.3, inf, inf]], [[0.1, 0.2, inf], [0.3, inf, inf]]], np.float32),
+         "pair_dist": np.array([[[1.0, 5.0, inf], [2.0, inf, inf]], [[2.0, 2.0, inf], [9.0, inf, inf]]], np.float32)}
+    rep, nko, nkt = ev.repeatability_from_batch(r, [3], True)
+    assert rep == {3: []} and nko == [5, 6] and nkt == [7, 8]                       # the last sample has no warped point in frame
+    assert ev.repeatability_from_batch(r, 3, False)[0] == {3: [3 / 8]}
+    d = ev.descriptor_from_batch(r, [2], True)[2]
+    assert d["tp_optical"] == [True, False, True] and d["tp_thermal"] == [True, True, False]
+    assert d["distance_optical"] == [float(np.float32(v)) for v in (0.1, 0.2, 0.3)]
+    assert d["m_score_optical"] == [0.25, 0.0] and d["m_score_thermal"] == [1.0, 0.0] and d["matching_kp_numbers"] == [1, 0]
+    assert d["n_gt_optical"] == 4 and d["n_gt_thermal"] == 6
+    d = ev.descriptor_from_batch(r, [2], False)[2]
+    assert d["n_gt_optical"] == 7 and d["n_gt_thermal"] == 11

@@ -109,6 +109,10 @@ _SIGNATURES = {
     "xp_detector_eval_gather": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     "xp_detector_eval_fill_dist": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_l, c_p],
     "xp_gather_match_points": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
+    "xp_pair_eval_warp_near": [c_p, c_p] + [c_i] * 4 + [c_p, c_p, c_i] + [c_p] * 4,
+    "xp_pair_eval_match_dist": [c_p] * 6 + [c_i, c_i, c_p, c_p],
+    "xp_pair_eval_count": [c_p] * 5 + [c_i, c_i, ctypes.POINTER(c_f), c_i, c_i] + [c_p] * 4,
+    "xp_pair_eval_corner_error": [c_p] * 4 + [c_i] * 3 + [c_p, c_p],
     "xp_find_homography": [c_p, c_p, c_p, c_i, c_i, c_f, c_i, ctypes.c_uint, c_p, c_p, c_p, c_p, c_sz, c_p],
     "xp_warp_perspective": [c_p, c_p, c_p] + [c_i] * 9 + [c_p],
     "xp_warp_perspective_masked": [c_p, c_p, c_p, c_p] + [c_i] * 9 + [c_p],

@@ -6,6 +6,12 @@
     python -m xpoint_amd.cli export    -y configs/config_export_keypoints.yaml -m model_weights/XPoint-EXP1 -v latest -o labels.npz
                                        [-i 0] [-n all] [-s 0] [--chunk K]
     python -m xpoint_amd.cli train     -y configs/cmt.yaml [-w <output_directory>/e20.model] [-s 0]
+    python -m xpoint_amd.cli benchmark -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-s 0] [-o out.json]
+
+`benchmark` is the -e half of benchmark.py:175-249 (see `benchmark`): repeatability, NN-mAP, M-score and homography correctness over the WHOLE
+folder dataset in batches of prediction.batchsize (evaluation.compute_metrics_batched), with the script's threshold lists (1..10 for the
+repeatability, keypoint and warp thresholds, [2] for RANSAC) and prediction.detection_threshold; it prints the script's result lines and, with
+-o, writes the JSON the script writes.  The script's timing experiment and plots are not part of it; -i and -n are not used.
 
 `train` is train.py (xpoint_amd.training.fit, whose docstring lists what is kept and what differs): the VMamba XPoint on pairs of a folder dataset
 with keypoint labels, Adam with weight decay and a device-side guard against non-finite gradients, the LR schedule, validation, `params.yaml`,
@@ -129,9 +135,101 @@ def evaluate_keypoints(args, config, dataset, net) -> dict:
     return res
 
 
-def main(argv=None):
+BENCHMARK_THRESHOLDS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10]      # benchmark.py:133-135: repeatability, keypoint distance and warp error
+BENCHMARK_RANSAC_THRESHOLDS = [2]                           # benchmark.py:136
+
+
+def _jsonable(x):
+    """Plain Python for json.dumps: numpy scalars and arrays become numbers and lists, dictionary keys become strings (as json.dumps does)."""
+    if isinstance(x, dict):
+        return {str(k): _jsonable(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_jsonable(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+def benchmark_results(out, config, model_dir, version, detection_threshold) -> dict:
+    """The dictionary benchmark.py:214-237 writes for one detection threshold, from compute_metrics' return: `repeatability`, `descriptor`
+    ({'th_kp_<th>': {'nn_map', 'm_score'}}), `homography` and the bookkeeping keys (without the timing experiment's entries)."""
+    ds = config['dataset']
+    res = {'repeatability': out['repeatability'],
+           'descriptor': {'th_kp_{}'.format(th): {k: out['descriptor'][th][k] for k in ('nn_map', 'm_score') if k in out['descriptor'][th]}
+                          for th in out['descriptor']},
+           'homography': out['homography'],
+           'model_dir': model_dir, 'model_version': version, 'height-width': '{},{}'.format(ds['height'], ds['width']),
+           'dataset': ds['filename'] if ds.get('filename') else ds['foldername'],
+           'nms': config['prediction']['nms'], 'detection_th': detection_threshold,
+           'threshold_keypoints_for_descriptor': list(BENCHMARK_THRESHOLDS), 'threshold_homography_epsilon': list(BENCHMARK_THRESHOLDS),
+           'threshold_repeatability_distance_th': list(BENCHMARK_THRESHOLDS), 'ransac_reproj_thresholds': list(BENCHMARK_RANSAC_THRESHOLDS)}
+    return _jsonable(res)
+
+
+def benchmark(args):
+    """The -e half of benchmark.py:175-249: evaluation.compute_metrics_batched over the whole folder dataset in batches of
+    prediction.batchsize with the script's threshold lists, its printed result lines, and with -o its JSON (benchmark_results).  The timing
+    experiment and the plots of the script are not part of this; HDF5 datasets are not supported."""
+    import json
+    from . import evaluation, predict
+    random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
+    config = load_config(args.yaml_config, args.model_dir)
+    if config['dataset'].get('filename') is not None or config['dataset'].get('foldername') is None:
+        raise SystemExit("benchmark: only folder datasets are supported (dataset.foldername)")
+    try:                                                                         # benchmark.py:57-60
+        config['model']['homography_regression_head']['check'] = not bool(config['prediction']['disable_hmhead'])
+    except (KeyError, TypeError):
+        pass
+    config['prediction'] = predict._cfg(config.get('prediction'))
+    if not torch.cuda.is_available():
+        raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
+    print('Predicting on device: {}'.format(args.device))
+    dataset, net = build(config, args.model_dir, args.version, args.device)
+    pred = config['prediction']
+    bs = int(pred.get('batchsize', 1))
+    detection_threshold = pred['detection_threshold']
+    print("MODEL : ", args.model_dir)
+    print("Keypoint detection threshold : ", [detection_threshold])
+
+    def loader():
+        for i0 in range(0, len(dataset), bs):
+            yield dataset.load_batch(list(range(i0, min(i0 + bs, len(dataset)))), args.device)
+
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        out = evaluation.compute_metrics_batched(net, loader(), args.device, config, detection_threshold,
+                                                 thresh_repeatability=list(BENCHMARK_THRESHOLDS), thresh_keypoints=list(BENCHMARK_THRESHOLDS),
+                                                 thresh_warp=list(BENCHMARK_THRESHOLDS), ransac_reproj_thresholds=list(BENCHMARK_RANSAC_THRESHOLDS))
+    dt = time.perf_counter() - t0
+    print("-----------repeatability Results:--------------")
+    rep = out["repeatability"]
+    print('Repeatability: {}'.format(rep['repeatability_mean']))
+    print('Number of optical keypoints: {}'.format(rep['n_kp_optical']))
+    print('Number of thermal keypoints: {}'.format(rep['n_kp_thermal']))
+    print("-------Descriptor Results:-------------")
+    for key in out["descriptor"]:
+        print('th kp : {}, NN-mAP: {}'.format(key, out["descriptor"][key]['nn_map']))
+        print('th kp : {}, M-Score: {}'.format(key, out["descriptor"][key]['m_score']))
+    print("-------Homography correctness Results:-------------")
+    for th in out["homography"]:
+        print('th ransac reprojection : {}, Homography correctness: {}'.format(th, out["homography"][th]['h_correctness']))
+    print(f"benchmark: {len(dataset)} pair(s), {dt * 1e3:.1f} ms")
+    res = benchmark_results(out, config, args.model_dir, args.version, detection_threshold)
+    if args.output:
+        d = os.path.dirname(args.output)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(args.output, 'w') as fh:
+            fh.write(json.dumps(res, indent=4))
+        print("-----done : ", args.output, "\n")
+    return res
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m xpoint_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('flow', choices=['align', 'keypoints', 'export', 'train'])
+    ap.add_argument('flow', choices=['align', 'keypoints', 'export', 'train', 'benchmark'])
     ap.add_argument('-y', '--yaml-config', default='configs/cipdp.yaml', help='YAML config file')
     ap.add_argument('-m', '--model-dir', default='model_weights/xpoint', help='Directory of the model')
     ap.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
@@ -143,13 +241,19 @@ def main(argv=None):
     ap.add_argument('-t', dest='threshold', default=3, type=int, help='keypoints -e: distance threshold for two keypoints to be considered a match')
     ap.add_argument('--save-warped', default=None, metavar='DIR', help='align -e: write the warped optical image of every sample to DIR/<name>_warped.png')
     ap.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
-    ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz')
+    ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz (benchmark: the result JSON)')
     ap.add_argument('--chunk', default=None, type=int, help='export: homographies per forward (does not change the result)')
     ap.add_argument('-w', '--weight-file', default=None, help='train: file containing the weights to initialize the weights (e<N>.model resumes at epoch N)')
     ap.add_argument('--device', default='cuda:0')
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.flow == 'export':
         return export(args)
+    if args.flow == 'benchmark':
+        return benchmark(args)
     if args.flow == 'train':
         return train(args)
     if args.count is None:

@@ -26,6 +26,11 @@ the same pairs seen from either side), and the N x M "distance to the nearest ke
 `xp_points_min_dist` returns the per-row minimum, which is all the metrics use.  The per-match bookkeeping (tp lists,
 sorting, precision / recall) is host numpy on a few thousand numbers, exactly as in the reference.
 
+The batched device form of the same metrics: pair_metrics_batched (one batch: keypoints, descriptors, ONE matcher call,
+the xp_pair_eval_* kernels, one batched homography estimate per RANSAC threshold, nothing read back when the list capacity is known) and
+compute_metrics_batched (compute_metrics' signature and return structure; `reference_quirks` chooses between the reference's per-sample
+overwrites and every sample counting).  `cli benchmark` and training.fit's validation metrics run on it.
+
 Reference behaviour kept on purpose (the goldens in tests/golden/g13 come from the reference's own code):
   * inside a batch the repeatability dict and the `n_gt_*` counts are OVERWRITTEN per sample, so they hold the last
     sample's value (benchmark_evaluation.py:447-461, 662-663) — which is why the reference's NN-mAP can exceed 1;
@@ -333,6 +338,289 @@ def compute_metrics(net, dataloader, device, config, keypoint_detection_threshol
     tw = thresh_warp if type(thresh_warp) is list else [thresh_warp]
     return {"repeatability": out_rep, "descriptor": compute_desc_dict(descriptor_metrics_dict),
             "homography": compute_homography_dict(overall_pts_dist_dict, tw)}
+
+
+# ------------------------------------------------------------------------------------------------
+# The same metrics for a whole batch on the device (DESIGN.md "Matching evaluation"; include/xpoint_hip.h, xp_pair_eval_*).
+# ------------------------------------------------------------------------------------------------
+PAIR_EVAL_MAX_THRESHOLDS = 16          # thresholds per xp_pair_eval_count launch (longer lists take several launches)
+
+
+def _as_list(x):
+    return x if type(x) is list else [x]
+
+
+def pair_eval_matrices(H_o, H_t):
+    """The 3 x 3 matrices of one batch, computed on the HOST one sample at a time exactly as the per-sample functions compute them (float32
+    torch .inverse(), gt = h_t @ h_o.inverse(); a batched or device inverse would have other bits).  H_o, H_t: (B, 3, 3).  Returns float64 numpy
+    arrays: rep_map1, rep_map2, desc_map1 (2B, 9) — per image, optical images first — and gt (B, 9)."""
+    B = int(H_o.shape[0])
+    m1, m2, d1 = [[None] * (2 * B) for _ in range(3)]
+    gts = []
+    for b in range(B):
+        h_o = H_o[b].squeeze().double().cpu().float()
+        h_t = H_t[b].squeeze().double().cpu().float()
+        m1[b], m2[b] = h_o.inverse().numpy(), h_t.numpy()                 # compute_repeatability_for_sample: optical -> scene -> thermal
+        m1[B + b], m2[B + b] = h_t.inverse().numpy(), h_o.numpy()
+        gt = torch.mm(h_t, h_o.inverse())                                 # compute_descriptor_for_sample
+        d1[b], d1[B + b] = gt.numpy(), gt.inverse().numpy()
+        gts.append(gt.numpy())
+    f = lambda rows: np.stack([np.asarray(r, dtype=np.float64).reshape(9) for r in rows])
+    return f(m1), f(m2), f(d1), f(gts)
+
+
+def _pe_warp_near(kp, counts, P, cap, H, W, map1, map2, truncate):
+    dev = kp.device
+    warped = torch.empty((2 * P, cap, 2), dtype=torch.float64, device=dev)
+    inframe = torch.empty((2 * P, cap), dtype=torch.uint8, device=dev)
+    near = torch.empty((2 * P, cap), dtype=torch.float32, device=dev)
+    _lib.call("xp_pair_eval_warp_near", ptr(kp), ptr(counts), P, cap, int(H), int(W), ptr(map1), ptr(map2), int(bool(truncate)),
+              ptr(warped), ptr(inframe), ptr(near), _lib.current_stream(dev))
+    return warped, inframe, near
+
+
+def _pe_match_dist(kp, counts, warped, res, P, cap):
+    dist = torch.empty((2, P, cap), dtype=torch.float32, device=kp.device)
+    _lib.call("xp_pair_eval_match_dist", ptr(kp), ptr(counts), ptr(warped), ptr(res["match_q"]), ptr(res["match_t"]), ptr(res["match_count"]),
+              P, cap, ptr(dist), _lib.current_stream(kp.device))
+    return dist
+
+
+def _pe_count(near, inframe, counts, dist, match_count, P, cap, thresholds, inframe_only):
+    """(near_cnt (2, P, T), match_cnt (2, P, T), n_inframe (2, P)) int32 on the device; one launch per 16 thresholds."""
+    dev = near.device
+    ths = [float(t) for t in thresholds]
+    if not ths:
+        raise ValueError("pair evaluation: the threshold list is empty")
+    near_cnt, match_cnt = [], []
+    n_in = torch.empty((2, P), dtype=torch.int32, device=dev)
+    for k0 in range(0, len(ths), PAIR_EVAL_MAX_THRESHOLDS):
+        part = ths[k0:k0 + PAIR_EVAL_MAX_THRESHOLDS]
+        T = len(part)
+        nc = torch.empty((2, P, T), dtype=torch.int32, device=dev)
+        mc = torch.zeros((2, P, T), dtype=torch.int32, device=dev)
+        _lib.call("xp_pair_eval_count", ptr(near), ptr(inframe), ptr(counts), ptr(dist), ptr(match_count), P, cap, (ctypes.c_float * T)(*part), T,
+                  int(bool(inframe_only)), ptr(nc), ptr(mc), ptr(n_in), _lib.current_stream(dev))
+        near_cnt.append(nc); match_cnt.append(mc)
+    return torch.cat(near_cnt, 2), torch.cat(match_cnt, 2), n_in
+
+
+def _pe_corner_error(H_gt, H_est, n_inliers, match_count, P, H, W):
+    err = torch.empty((P,), dtype=torch.float64, device=H_gt.device)
+    H_est = H_est.contiguous()
+    _lib.call("xp_pair_eval_corner_error", ptr(H_gt), ptr(H_est), ptr(n_inliers), ptr(match_count), P, int(H), int(W), ptr(err),
+              _lib.current_stream(H_gt.device))
+    return err
+
+
+def pair_metrics_batched(prob_rep_o, prob_rep_t, prob_desc_o, prob_desc_t, desc_o, desc_t, H_o, H_t, detection_threshold, thresh_repeatability,
+                         thresh_keypoints, ransac_reproj_thresholds, cap=None, mask_rep_o=None, mask_rep_t=None):
+    """compute_repeatability_for_sample + compute_descriptor_for_sample + compute_pts_dist_for_sample for ONE batch as device work.
+
+    prob_rep_* (B, 1, H, W): the heat maps of the repeatability keypoints, nonzero((prob > thr) * mask_rep_*) (mask_rep_*: the valid masks, or
+    None); prob_desc_* (B, 1, H, W): the (already masked) heat maps of the descriptor keypoints, nonzero(prob > thr); desc_* (B, D, Hc, Wc) the
+    dense descriptor maps; H_o, H_t (B, 3, 3) the sample homographies — HOST tensors (pair_eval_matrices prepares the B x 9 numbers on the
+    host, one upload per batch).  cap: the capacity of the ragged lists; when it is given (prediction.topk > 0 bounds every list) nothing is
+    read back, otherwise the largest count is read once.
+
+    Launch plan: two xp_extract_keypoints (each over the 2B stacked maps), one xp_sample_descriptors, ONE xp_match_mnn over the B pairs (the
+    per-sample functions match every sample twice), xp_pair_eval_warp_near + xp_pair_eval_count for the repeatability set, warp_near +
+    match_dist + count for the descriptor set, xp_gather_match_points, and per RANSAC threshold one xp_find_homography and one
+    xp_pair_eval_corner_error.  The reference's match order (sorted by distance, equal distances by ascending query index for query = optical
+    and by ascending target index for query = thermal) comes from torch's stable sort on the device.
+
+    Returns device tensors (B pairs, Tr / Tk / R thresholds), directions [0] = optical image is the query, [1] = thermal:
+      n_kp (2B)                      repeatability keypoints per image, optical images first
+      rep_count (2, B, Tr), rep_inframe (2, B)      warped in-frame points with a keypoint of the other image within th / their number
+      n_desc_kp (2B), n_gt (2, B, Tk), desc_inframe (2, B), match_ok (2, B, Tk), match_count (B)
+      match_dist (2, B, cap), pair_dist (2, B, cap)  matcher distance and |warped - matched| per match, in the reference's order (+inf filler)
+      corner_error (R, B) float64, H_est (R, B, 3, 3), n_inliers (R, B)
+      overflow ()  bool: a list was longer than cap and is truncated (compute_metrics_batched refuses such a result)
+    Homography estimates: xp_find_homography seeds its hypotheses with the PAIR INDEX, so sample p of a batch draws as pair p while the
+    per-sample path always draws as pair 0: corner_error of sample 0 equals compute_pts_dist_for_sample's, the other samples get the batched
+    estimator's (equally valid) estimate."""
+    if not (torch.is_tensor(prob_rep_o) and prob_rep_o.is_cuda):
+        raise ValueError("pair_metrics_batched: the heat maps must be GPU tensors (no CPU fallback)")
+    H, W = (int(v) for v in prob_rep_o.shape[-2:])
+    B = prob_rep_o.numel() // (H * W)
+    dev = prob_rep_o.device
+    ths_rep, ths_kp, ths_ransac = _as_list(thresh_repeatability), _as_list(thresh_keypoints), _as_list(ransac_reproj_thresholds)
+    stack = lambda a, b: torch.cat([a.reshape(B, H, W).float(), b.reshape(B, H, W).float()])
+    with torch.cuda.device(dev):
+        mask = None
+        if mask_rep_o is not None or mask_rep_t is not None:
+            ones = torch.ones((B, H, W), dtype=torch.bool, device=dev)
+            mask = torch.cat([ones if m is None else (m.reshape(B, H, W).to(dev) != 0) for m in (mask_rep_o, mask_rep_t)])
+        kp_r, cnt_r = utils.extract_keypoints(stack(prob_rep_o, prob_rep_t), detection_threshold, mask, cap)
+        kp_d, cnt_d = utils.extract_keypoints(stack(prob_desc_o, prob_desc_t), detection_threshold, None, cap)
+        if cap is None:
+            cap = max(1, int(torch.maximum(cnt_r.max(), cnt_d.max()).item()))                  # the one read-back of an unbounded batch
+            kp_r, kp_d = kp_r[:, :cap].contiguous(), kp_d[:, :cap].contiguous()
+        cap = int(cap)
+        overflow = (cnt_r > cap).any() | (cnt_d > cap).any()
+        cnt_r, cnt_d = cnt_r.clamp(max=cap), cnt_d.clamp(max=cap)
+        tables = np.concatenate(pair_eval_matrices(H_o, H_t))
+        tables = torch.from_numpy(tables).to(dev)                                               # the one upload: (7B, 9) float64
+        rep1, rep2, desc1, gt = tables[:2 * B], tables[2 * B:4 * B], tables[4 * B:6 * B], tables[6 * B:]
+
+        # repeatability: two truncating maps, counts over the in-frame points
+        _, in_r, near_r = _pe_warp_near(kp_r, cnt_r, B, cap, H, W, rep1, rep2, True)
+        rep_count, _, rep_inframe = _pe_count(near_r, in_r, cnt_r, None, None, B, cap, ths_rep, True)
+
+        # descriptors: one sampling call, one matcher call, one float map per direction
+        nhwc = torch.cat([desc_o, desc_t]).permute(0, 2, 3, 1).contiguous().float()
+        Hc, Wc, D = (int(v) for v in nhwc.shape[1:])
+        d = torch.zeros((2 * B, cap, D), dtype=torch.float32, device=dev)
+        _lib.call("xp_sample_descriptors", ptr(kp_d), ptr(cnt_d), ptr(nhwc), ptr(d), 2 * B, cap, Hc, Wc, D, H, W, _lib.current_stream(dev))
+        res = utils.match_descriptors(d[:B], d[B:], cnt_d, "strict_mnn")
+        mcount = res["match_count"]
+        warped_d, in_d, near_d = _pe_warp_near(kp_d, cnt_d, B, cap, H, W, desc1, None, False)
+        pd = _pe_match_dist(kp_d, cnt_d, warped_d, res, B, cap)
+        n_gt, match_ok, desc_inframe = _pe_count(near_d, in_d, cnt_d, pd, mcount, B, cap, ths_kp, False)
+
+        # the reference's order of the two match lists
+        live = torch.arange(cap, device=dev)[None, :] < mcount[:, None]
+        dkey = torch.where(live, res["match_d"], torch.full_like(res["match_d"], float("inf")))
+        order_o = torch.sort(dkey, dim=1, stable=True).indices
+        tkey = torch.where(live, res["match_t"], torch.full_like(res["match_t"], 2 ** 31 - 1))
+        by_t = torch.sort(tkey, dim=1, stable=True).indices
+        order_t = by_t.gather(1, torch.sort(dkey.gather(1, by_t), dim=1, stable=True).indices)
+        match_dist = torch.stack([dkey.gather(1, order_o), dkey.gather(1, order_t)])
+        pair_dist = torch.stack([pd[0].gather(1, order_o), pd[1].gather(1, order_t)])
+
+        # homography: correspondences in the match list's own order (ascending query index), as compute_pts_dist_for_sample
+        src = torch.empty((B, cap, 2), dtype=torch.float32, device=dev); dst = torch.empty_like(src)
+        _lib.call("xp_gather_match_points", ptr(kp_d), ptr(res["match_q"]), ptr(res["match_t"]), ptr(mcount), B, cap, ptr(src), ptr(dst),
+                  _lib.current_stream(dev))
+        errs, ests, inls = [], [], []
+        for th in ths_ransac:
+            H_est, _, n_inl = utils.find_homography_batched(src, dst, mcount, th)
+            errs.append(_pe_corner_error(gt, H_est, n_inl, mcount, B, H, W)); ests.append(H_est); inls.append(n_inl)
+    return dict(n_kp=cnt_r, rep_count=rep_count, rep_inframe=rep_inframe, n_desc_kp=cnt_d, n_gt=n_gt, desc_inframe=desc_inframe, match_ok=match_ok,
+                match_count=mcount, match_dist=match_dist, pair_dist=pair_dist, corner_error=torch.stack(errs), H_est=torch.stack(ests),
+                n_inliers=torch.stack(inls), overflow=overflow)
+
+
+def download_pair_metrics(batches):
+    """The results of pair_metrics_batched calls as numpy, one device -> host copy per result array for ALL batches."""
+    if not batches:
+        return []
+    out = [{} for _ in batches]
+    for key in batches[0]:
+        flat = torch.cat([b[key].reshape(-1) for b in batches]).cpu().numpy()
+        o = 0
+        for dst, b in zip(out, batches):
+            n = b[key].numel()
+            dst[key] = flat[o:o + n].reshape(tuple(b[key].shape))
+            o += n
+    return out
+
+
+def repeatability_from_batch(r, thresh_repeatability, reference_quirks=True):
+    """compute_repeatability_for_sample's returns from one downloaded batch: ({th: [..]}, n_kp_optical list, n_kp_thermal list).  With
+    reference_quirks the dict holds the LAST sample's entry only (the reference overwrites it per sample), else one entry per sample that
+    has a warped point in frame."""
+    B = r["rep_inframe"].shape[1]
+    out = {}
+    for k, th in enumerate(_as_list(thresh_repeatability)):
+        member = []
+        for b in ([B - 1] if reference_quirks else range(B)):
+            n = int(r["rep_inframe"][0, b]) + int(r["rep_inframe"][1, b])
+            if n > 0:
+                member.append((int(r["rep_count"][1, b, k]) + int(r["rep_count"][0, b, k])) / n)
+        out[th] = member
+    return out, [int(v) for v in r["n_kp"][:B]], [int(v) for v in r["n_kp"][B:]]
+
+
+def descriptor_from_batch(r, thresh_keypoints, reference_quirks=True):
+    """compute_descriptor_for_sample's return from one downloaded batch.  With reference_quirks n_gt_* is the LAST sample's (overwritten per
+    sample in the reference), else the sum over the samples."""
+    B = r["match_count"].shape[0]
+    out = {}
+    for k, th in enumerate(_as_list(thresh_keypoints)):
+        e = {}
+        thf = np.float32(th)
+        for di, spec in enumerate(("optical", "thermal")):
+            tp, dist, ms = [], [], []
+            for b in range(B):
+                n = int(r["match_count"][b])
+                tp += (r["pair_dist"][di, b, :n] <= thf).tolist()
+                dist += r["match_dist"][di, b, :n].tolist()
+                n_in = int(r["desc_inframe"][di, b])
+                ms.append(float(int(r["match_ok"][di, b, k])) / n_in if n_in > 0 else 0.0)
+            e[f"tp_{spec}"], e[f"distance_{spec}"], e[f"m_score_{spec}"] = tp, dist, ms
+            e[f"n_gt_{spec}"] = int(r["n_gt"][di, B - 1, k]) if reference_quirks else int(r["n_gt"][di, :, k].sum())
+        e["matching_kp_numbers"] = [(int(r["match_ok"][0, b, k]) + int(r["match_ok"][1, b, k])) // 2 for b in range(B)]
+        out[th] = e
+    return out
+
+
+def compute_metrics_batched(net, dataloader, device, config, keypoint_detection_threshold=0.015, thresh_repeatability=3, thresh_keypoints=2,
+                            thresh_warp=2, ransac_reproj_thresholds=3, reference_quirks=True):
+    """compute_metrics with the per-sample functions replaced by pair_metrics_batched: same arguments, same return structure.  Per batch: the
+    forward, ONE box_nms over the four stacked heat-map sets (the NMS decides every image on its own), one pair_metrics_batched (no read-back
+    when prediction.topk > 0 bounds the lists); the per-batch results stay on the device and come back in one pass at the end
+    (download_pair_metrics); precision / recall are compute_desc_dict / compute_homography_dict, unchanged.
+
+    reference_quirks=True keeps the reference's per-sample overwrites (the repeatability entry and n_gt_* of a batch are its LAST sample's), so
+    the repeatability and descriptor dictionaries equal compute_metrics'.  False uses every sample: one repeatability entry per sample and n_gt
+    summed over the samples, which bounds NN-mAP by 1.
+    Homography: sample p of a batch is estimated as pair p of xp_find_homography (see pair_metrics_batched); sample 0 of every batch equals
+    the per-sample path, the others are the batched estimator's estimates of the same correspondences."""
+    ths_rep, ths_kp = _as_list(thresh_repeatability), _as_list(thresh_keypoints)
+    rts = _as_list(ransac_reproj_thresholds)
+    pred = config['prediction']
+    m = pred['matching']
+    if m['method'] != 'bfmatcher' or m.get('knn_matches', False) or not m.get('method_kwargs', {}).get('crossCheck', False):
+        raise NotImplementedError("xpoint_amd.evaluation: the device matcher implements bfmatcher + crossCheck (the reference's configured mode)")
+    batches = []
+    for data in dataloader:
+        B = data['optical']['image'].shape[0]
+        for spec in ('optical', 'thermal'):
+            if 'homography' not in data[spec]:
+                data[spec]['homography'] = torch.eye(3, dtype=torch.float32).repeat(B, 1, 1)
+        H_optical, H_thermal = data['optical']['homography'], data['thermal']['homography']
+        data = utils.data_to_device(data, device)
+        if not net.takes_pair():
+            out_optical, out_thermal = net(data['optical']), net(data['thermal'])
+        else:
+            out_optical, out_thermal, _ = net(data)
+        mask_o, mask_t = data['optical']['valid_mask'], data['thermal']['valid_mask']
+        maps = [out_thermal['prob'] * mask_t, out_optical['prob'] * mask_o, out_optical['prob'], out_thermal['prob']]
+        cap = None
+        if pred['nms'] > 0:
+            stacked = utils.box_nms(torch.cat([p.reshape(B, 1, *p.shape[-2:]).float() for p in maps]), pred['nms'], keypoint_detection_threshold,
+                                    keep_top_k=pred['topk'], on_cpu=pred.get('cpu_nms', False))
+            maps = list(stacked.split(B))
+            if pred['topk'] > 0:
+                cap = int(pred['topk'])
+        batches.append(pair_metrics_batched(maps[2], maps[3], maps[1], maps[0], out_optical['desc'], out_thermal['desc'], H_optical, H_thermal,
+                                            keypoint_detection_threshold, ths_rep, ths_kp, rts, cap=cap, mask_rep_o=mask_o, mask_rep_t=mask_t))
+    host = download_pair_metrics(batches)
+    repeatability = {th: [] for th in ths_rep}
+    n_kp_optical, n_kp_thermal = [], []
+    descriptor_metrics_dict = {th: {} for th in ths_kp}
+    overall_pts_dist_dict = {th: [] for th in rts}
+    for r in host:
+        if bool(r["overflow"]):
+            raise _lib.XPointHipError("compute_metrics_batched: a keypoint list is longer than its capacity (prediction.topk)")
+        rep, nko, nkt = repeatability_from_batch(r, ths_rep, reference_quirks)
+        for key, value in rep.items():
+            repeatability[key].extend(value)
+        n_kp_optical += nko; n_kp_thermal += nkt
+        for key, value in descriptor_from_batch(r, ths_kp, reference_quirks).items():
+            for key2, value2 in value.items():
+                if key2.startswith("n_gt"):
+                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, 0) + value2
+                else:
+                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, []) + value2
+        for i, th in enumerate(rts):
+            overall_pts_dist_dict[th] += [float(v) for v in r["corner_error"][i]]
+    out_rep = {'repeatability_mean': {k: np.mean(v) for k, v in repeatability.items()},
+               'n_kp_optical': np.mean(n_kp_optical), 'n_kp_thermal': np.mean(n_kp_thermal)}
+    out_rep['n_kp_avg'] = (out_rep['n_kp_optical'] + out_rep['n_kp_thermal']) / 2.0
+    return {"repeatability": out_rep, "descriptor": compute_desc_dict(descriptor_metrics_dict),
+            "homography": compute_homography_dict(overall_pts_dist_dict, _as_list(thresh_warp))}
 
 
 # ------------------------------------------------------------------------------------------------

@@ -8,7 +8,10 @@ training.scheduler.{use_scheduler, type: StepLR | ExponentialLR, step_size, gamm
 keypoints}; `num_worker` and `allow_gpu` are accepted and ignored; `training.mixed_precision: true` is refused with XPointNet's message.  New,
 optional: training.validation.foldername (the folder-mode counterpart of the reference's `filename`), training.log_every (a `batch_loss` record every
 that many steps), training.max_norm (global-norm clipping, off by default as in the reference), training.ss2d_core ('routes', the default, or 'pixel':
-training.set_ss2d_core; checked before anything is built and written into params.yaml).
+training.set_ss2d_core; checked before anything is built and written into params.yaml), training.validation.compute_metrics with
+training.validation.metric_thresholds (default [3]): after the validation loss, evaluation.compute_metrics_batched(reference_quirks=False) of the
+inference network on the validation pairs (prediction settings from config['prediction'] over predict.DEFAULT_PREDICTION) — `validation_metrics`
+in the history and validation/{repeatability, nn_map, m_score, h_correctness}_<th> in learningcurve.jsonl; without the key nothing changes.
 
 What is kept from train.py: params.yaml with the four sections at the start; the weights of -w loaded with strict=False after
 fix_model_weigth_keys, zero loaded keys refused; the start epoch parsed from an `e<N>.model` name; loss.space_to_depth_ratio from the model; Adam with
@@ -79,6 +82,47 @@ def _dataset(ds_cfg):
     return datasets.ImagePairDataset(ds_cfg)
 
 
+def validation_metric_thresholds(val):
+    """The thresholds of the matching metrics of a validation pass, or None when they are off.  training.validation.compute_metrics is read only
+    when a validation folder is in use (compute_validation_loss); metric_thresholds (default [3]) must be a non-empty list of at most 16
+    positive numbers, each of which serves as repeatability distance, keypoint distance and warp-error threshold."""
+    val = val or {}
+    if not val.get('compute_validation_loss', False) or not val.get('compute_metrics', False):
+        return None
+    if val.get('foldername') is None:
+        raise ValueError("fit: training.validation.foldername is needed (folder datasets only; the reference's `filename` is an HDF5 file)")
+    ths = val.get('metric_thresholds', [3])
+    ok = isinstance(ths, (list, tuple)) and 1 <= len(ths) <= 16 and all(
+        isinstance(t, (int, float)) and not isinstance(t, bool) and np.isfinite(t) and t > 0 for t in ths)
+    if not ok or len(set(ths)) != len(ths):
+        raise ValueError(f"fit: training.validation.metric_thresholds must be a list of 1 to 16 distinct positive numbers (got {ths!r})")
+    return list(ths)
+
+
+def _validation_metrics(net, model, val_dataset, bs, device, config, ths):
+    """evaluation.compute_metrics_batched(reference_quirks=False) of the inference network with the model's current weights on the validation
+    pairs as they are (no augmentation: identity homographies), as plain numbers per threshold."""
+    from .. import evaluation, predict
+    net.load_state_dict(model.state_dict(), strict=False)
+    net.eval()
+    cfg = {'prediction': predict._cfg(config.get('prediction'))}
+    ransac = cfg['prediction'].get('reprojection_threshold', 3)
+
+    def loader():
+        for k in range(0, len(val_dataset), bs):
+            yield val_dataset.load_batch(list(range(k, min(k + bs, len(val_dataset)))), device)
+
+    out = evaluation.compute_metrics_batched(net, loader(), device, cfg, cfg['prediction']['detection_threshold'], list(ths), list(ths), list(ths),
+                                             [ransac], reference_quirks=False)
+    hom = out['homography'][ransac]
+    return {'repeatability': {th: float(out['repeatability']['repeatability_mean'][th]) for th in ths},
+            'nn_map': {th: float(out['descriptor'][th]['nn_map']) for th in ths},
+            'm_score': {th: float(out['descriptor'][th]['m_score']) for th in ths},
+            'h_correctness': {th: float(hom['h_correctness']['epsilon_warp_th' + str(th)]) for th in ths},
+            'average_h_error': float(hom['average_h_error']),
+            'n_kp_optical': float(out['repeatability']['n_kp_optical']), 'n_kp_thermal': float(out['repeatability']['n_kp_thermal'])}
+
+
 def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True):
     """Trains models.XPoint(config['model']) as the module docstring says and returns the per-epoch means: {'epoch': [N, ...], 'loss': [...],
     'components': [{...}, ...], 'validation_loss': [... or None], 'validation_components': [...], 'learning_rate': [...], 'skipped_steps': [...]}
@@ -88,6 +132,7 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
     if tr.get('mixed_precision', False):
         raise NotImplementedError(MIXED_PRECISION_REFUSAL)
     core = check_ss2d_core(tr.get('ss2d_core', 'routes'), "fit: training.ss2d_core")
+    metric_ths = validation_metric_thresholds(tr.get('validation'))
     net = getattr(models, config['model'].get('type', 'XPoint'))(config['model'])
     XPointNet.check_config(net.config)
     device = torch.device(device)
@@ -180,7 +225,7 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
                     if log_every and (step + 1) % log_every == 0:
                         write('batch', step + 1, dict({'batch_loss': float(loss)}, **{'batch_loss/' + k: float(v) for k, v in components.items()}))
 
-                val_loss, val_components = None, {}
+                val_loss, val_components, val_metrics = None, {}, None
                 if val_dataset is not None and epoch % int(val.get('every_nth_epoch', 1)) == 0:
                     model.eval()
                     total = torch.zeros((), dtype=torch.float32, device=device)
@@ -196,6 +241,8 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
                             loss, components = loss_fn(loss_input)
                             total += loss
                             _add(val_components, components)
+                        if metric_ths is not None:
+                            val_metrics = _validation_metrics(net, model, val_dataset, bs, device, config, metric_ths)
                     model.train()
                     val_loss = float(total) / n_val
                     val_components = {k: v / n_val for k, v in val_components.items()}
@@ -207,6 +254,11 @@ def fit(config, weight_file=None, device="cuda:0", seed=0, resume_optimizer=True
                 scalars = dict({'loss': mean_loss, 'learning_rate': lr, 'skipped_steps': skipped}, **{'loss/' + k: v for k, v in mean_components.items()})
                 if val_loss is not None:
                     scalars.update({'validation_loss': val_loss}, **{'validation_loss/' + k: v for k, v in val_components.items()})
+                if val_metrics is not None:
+                    for name in ('repeatability', 'nn_map', 'm_score', 'h_correctness'):
+                        scalars.update({f'validation/{name}_{th}': v for th, v in val_metrics[name].items()})
+                if metric_ths is not None:
+                    history.setdefault('validation_metrics', []).append(val_metrics)
                 write('epoch', epoch + 1, scalars)
                 for k, v in (('epoch', epoch + 1), ('loss', mean_loss), ('components', mean_components), ('validation_loss', val_loss),
                              ('validation_components', val_components), ('learning_rate', lr), ('skipped_steps', skipped)):
