@@ -929,6 +929,58 @@ int xp_optim_adam_apply(float* const* params, const float* const* grads, const i
                         double beta2, double eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SyntheticShapes on the device (xpoint_amd/synthetic_shapes.py drives these; csrc/synth_shapes.hip; DESIGN.md "Synthetic shapes"; reference
+ * xpoint/utils/draw_primitives.py, xpoint/datasets/SyntheticShapes.py).  Frames are (B, H, W) f32, one channel, H, W <= 4096.  Every table is
+ * per image; nothing of image b depends on its batch neighbours, no launch count depends on B, two calls agree bit for bit.
+ *   xp_synth_background: frame = [u > thresholds[b]] with u the xp_aug_random_field uniform of (seed, sample_ids[b], XP_SYNTH_KEY_BACKGROUND),
+ *     then n_blobs (<= 256) filled circles, the last covering one wins: blob_geom (B, n_blobs, 4) int32 = (cx, cy, r, 0), inside iff
+ *     dx^2 + dy^2 <= r^2; colour = raw, or (raw + 0.5) % 1 where |raw - m| < min_contrast, m = the mean of the thresholded field (an integer
+ *     count / (H W), written to field_mean (B) f64); blob_raw (B, n_blobs) f64.  count_ws: B * XP_SYNTH_PARTIALS ints.  Two launches.
+ *   xp_synth_box_blur: cv2.blur(src, (k, k)) with k = ksizes[b] >= 1 (any parity, anchor k / 2, any size against the frame), normalised,
+ *     BORDER_REFLECT_101; rows into tmp, columns into dst (dst may be src).  Window sums are f64.  Two launches.
+ *   xp_synth_resolve_colours: bg_mean (B) f64 = the mean of `background` (f64 partial sums in a fixed order; partial_ws: B * XP_SYNTH_PARTIALS
+ *     doubles), then colours (B, n_records) f32 from the rules, in order, in f64: rules (B, n_records, 4) int32 = (kind, ref0, ref1, candidate
+ *     offset), rule_values (B, n_records, 2) f64 = (v, m).  XP_SYNTH_RULE_ABS: v.  _CONTRAST: v, or (v + 0.5) % 1 where |v - bg_mean| < m.
+ *     _DIFFERENT: the first of the XP_SYNTH_CANDIDATES values at candidates[b][offset ..] that differs by >= m from the colours of records ref0
+ *     and ref1 (each < the record's own index, or -1), else the last.  _REL: (colour[ref0] + m) % 1.  n_records <= XP_SYNTH_MAX_RECORDS.
+ *   xp_synth_rasterise: in place over the frame; records (B, n_records, XP_SYNTH_RECORD_INTS) int32 = kind, bounding box x0 y0 x1 y1
+ *     (inclusive), n, 16 geometry words, 2 spare.  The last record that covers a pixel gives its colour.  _CIRCLE (cx, cy; n = r):
+ *     dx^2 + dy^2 <= r^2.  _SEGMENT (x1, y1, x2, y2; n = thickness t): within t / 2 of the segment: 4 |AP|^2 <= t^2 beyond either end,
+ *     4 cross^2 <= t^2 len^2 between.  _POLYGON (n <= 8 vertices x, y): even-odd over half-open crossings, or on an edge.  _ELLIPSE (cx, cy,
+ *     ax, ay, then cos and sin of the angle as two f64): ((dx cos + dy sin) / ax)^2 + ((dy cos - dx sin) / ay)^2 <= 1 in f64, a half axis of
+ *     0 taken as 0.5.  _NOISE: every pixel = the uniform of (seed, sample_ids[b], XP_SYNTH_KEY_NOISE).  |coordinates| <= 16383.
+ *   xp_synth_resize: cv2.resize INTER_LINEAR (B, H, W) -> (B, h, w): source coordinate (d + 0.5) (H / h) - 0.5 in f64, taps clamped to the
+ *     frame, f32 weights, rows first: (t00 (1 - wx) + t01 wx) (1 - wy) + (t10 (1 - wx) + t11 wx) wy.
+ *   xp_synth_scatter_points: map (B, h, w) u8 = 0, then 1 at the first counts[b] (<= cap) points of points (B, cap, 2) int32 (y, x) that lie
+ *     inside. */
+#define XP_SYNTH_PARTIALS 128
+#define XP_SYNTH_MAX_RECORDS 128
+#define XP_SYNTH_RECORD_INTS 24
+#define XP_SYNTH_CANDIDATES 21
+#define XP_SYNTH_KEY_BACKGROUND 6
+#define XP_SYNTH_KEY_NOISE 7
+#define XP_SYNTH_NOP 0
+#define XP_SYNTH_CIRCLE 1
+#define XP_SYNTH_SEGMENT 2
+#define XP_SYNTH_POLYGON 3
+#define XP_SYNTH_ELLIPSE 4
+#define XP_SYNTH_NOISE 5
+#define XP_SYNTH_RULE_ABS 0
+#define XP_SYNTH_RULE_CONTRAST 1
+#define XP_SYNTH_RULE_DIFFERENT 2
+#define XP_SYNTH_RULE_REL 3
+int xp_synth_background(float* frame, unsigned long long seed, const int* sample_ids, const float* thresholds, const int* blob_geom,
+                        const double* blob_raw, int n_blobs, double min_contrast, int* count_ws, double* field_mean, int B, int H, int W,
+                        void* stream);
+int xp_synth_box_blur(const float* src, float* tmp, float* dst, const int* ksizes, int B, int H, int W, void* stream);
+int xp_synth_resolve_colours(const float* background, const int* rules, const double* rule_values, const double* candidates, int n_records,
+                             int n_candidates, double* partial_ws, float* colours, double* bg_mean, int B, int H, int W, void* stream);
+int xp_synth_rasterise(float* frame, const int* records, const float* colours, unsigned long long seed, const int* sample_ids, int n_records,
+                       int B, int H, int W, void* stream);
+int xp_synth_resize(const float* src, float* dst, int B, int H, int W, int h, int w, void* stream);
+int xp_synth_scatter_points(const int* points, const int* counts, int cap, uint8_t* map, int B, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the
  * reference's wall-clock brackets, benchmark_evaluation.py:12-37).  Off by default.  xp_prof_filter(tag)
  * restricts recording to one kernel tag (NULL/"" = all).  xp_prof_count / xp_prof_get synchronise on the

@@ -159,6 +159,12 @@ _SIGNATURES = {
     "xp_optim_grad_sumsq": [c_p, c_p, c_i, c_p, c_sz, ctypes.POINTER(c_l), c_p],
     "xp_optim_step_header": [c_p, c_l, c_p, c_d, c_d, c_d, c_i, c_p],
     "xp_optim_adam_apply": [c_p] * 4 + [c_i, c_p, c_p, c_l, c_p] + [c_d] * 5 + [c_p],
+    "xp_synth_background": [c_p, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_i, c_d, c_p, c_p, c_i, c_i, c_i, c_p],
+    "xp_synth_box_blur": [c_p] * 4 + [c_i] * 3 + [c_p],
+    "xp_synth_resolve_colours": [c_p] * 4 + [c_i, c_i] + [c_p] * 3 + [c_i] * 3 + [c_p],
+    "xp_synth_rasterise": [c_p, c_p, c_p, ctypes.c_uint64, c_p] + [c_i] * 4 + [c_p],
+    "xp_synth_resize": [c_p, c_p] + [c_i] * 5 + [c_p],
+    "xp_synth_scatter_points": [c_p, c_p, c_i, c_p] + [c_i] * 3 + [c_p],
     "xp_prof_enable": [c_i],
     "xp_prof_filter": [ctypes.c_char_p],
     "xp_prof_reset": [],

@@ -1,4 +1,4 @@
-"""Thin command-line front ends of the two prediction flows, the label export and the training run, with the reference scripts' arguments
+"""Thin command-line front ends of the two prediction flows, the label export, the training run and the synthetic-shapes generator, with the reference scripts' arguments
 (predict_align_image_pair.py:24-37, predict_keypoints.py: the same -y / -m / -v / -i / -s options; train.py: -y / -w):
 
     python -m xpoint_amd.cli align     -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-i 0] [-n 1] [-s 0] [-e] [-o out.npz]
@@ -7,6 +7,11 @@
                                        [-i 0] [-n all] [-s 0] [--chunk K]
     python -m xpoint_amd.cli train     -y configs/cmt.yaml [-w <output_directory>/e20.model] [-s 0]
     python -m xpoint_amd.cli benchmark -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-s 0] [-o out.json]
+    python -m xpoint_amd.cli synth     -y configs/config_synthetic_shapes.yaml -n 16 -o shapes.npz [-i 0] [-s 0]
+
+`synth` is show_synthetic_images.py without the plots: samples -i .. -i + n - 1 of the SyntheticShapes dataset of the YAML's `dataset:` block
+(xpoint_amd.synthetic_shapes: rendered on the GPU, then augmented as the block says), written to -o as image (n, 1, h, w) f32, keypoints
+(n, h, w) bool, valid_mask (n, 1, h, w) bool and is_optical (n, 1) bool.  Sample i depends on (-s, i) alone.  -m, -v are not used.
 
 `benchmark` is the -e half of benchmark.py:175-249 (see `benchmark`): repeatability, NN-mAP, M-score and homography correctness over the WHOLE
 folder dataset in batches of prediction.batchsize (evaluation.compute_metrics_batched), with the script's threshold lists (1..10 for the
@@ -229,7 +234,7 @@ def benchmark(args):
 
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m xpoint_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('flow', choices=['align', 'keypoints', 'export', 'train', 'benchmark'])
+    ap.add_argument('flow', choices=['align', 'keypoints', 'export', 'train', 'benchmark', 'synth'])
     ap.add_argument('-y', '--yaml-config', default='configs/cipdp.yaml', help='YAML config file')
     ap.add_argument('-m', '--model-dir', default='model_weights/xpoint', help='Directory of the model')
     ap.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
@@ -241,7 +246,7 @@ def build_parser():
     ap.add_argument('-t', dest='threshold', default=3, type=int, help='keypoints -e: distance threshold for two keypoints to be considered a match')
     ap.add_argument('--save-warped', default=None, metavar='DIR', help='align -e: write the warped optical image of every sample to DIR/<name>_warped.png')
     ap.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
-    ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz (benchmark: the result JSON)')
+    ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz (benchmark: the result JSON; synth: the samples)')
     ap.add_argument('--chunk', default=None, type=int, help='export: homographies per forward (does not change the result)')
     ap.add_argument('-w', '--weight-file', default=None, help='train: file containing the weights to initialize the weights (e<N>.model resumes at epoch N)')
     ap.add_argument('--device', default='cuda:0')
@@ -256,6 +261,8 @@ def main(argv=None):
         return benchmark(args)
     if args.flow == 'train':
         return train(args)
+    if args.flow == 'synth':
+        return synth_shapes(args)
     if args.count is None:
         args.count = 1
 
@@ -316,6 +323,36 @@ def train(args):
         raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
     from . import training
     return training.fit(config, weight_file=args.weight_file, device=args.device, seed=args.seed)
+
+
+def synth_shapes(args):
+    """show_synthetic_images.py without the plots (see the module docstring)."""
+    if not args.output:
+        raise SystemExit("synth: -o/--output (.npz) is required")
+    with open(args.yaml_config, 'r') as f:
+        config = yaml.load(f, Loader=yaml.FullLoader)
+    ds = dict(config.get('dataset', {}))
+    if ds.get('type', 'SyntheticShapes') != 'SyntheticShapes':
+        raise SystemExit(f"synth: dataset.type must be 'SyntheticShapes', got {ds.get('type')!r}")
+    ds.pop('type', None)
+    if not torch.cuda.is_available():
+        raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
+    from . import synthetic_shapes
+    dataset = synthetic_shapes.SyntheticShapes(ds)
+    n = 1 if args.count is None else args.count
+    bs = int(config.get('training', {}).get('batchsize', 32))
+    parts = []
+    t0 = time.perf_counter()
+    for i0 in range(args.index, args.index + n, bs):
+        parts.append(dataset.load_batch(list(range(i0, min(i0 + bs, args.index + n))), args.device, seed=args.seed))
+    torch.cuda.synchronize()
+    out = {k: torch.cat([p[k] for p in parts]).cpu().numpy() for k in ('image', 'keypoints', 'valid_mask', 'is_optical')}
+    print(f"synth: {n} sample(s) of {tuple(out['image'].shape[2:])}, {int(out['keypoints'].sum())} keypoints, {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    d = os.path.dirname(args.output)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    np.savez(args.output, **out)
+    return out
 
 
 def export(args):

@@ -96,6 +96,22 @@ class XPointNet(TrainModule):
             raise ValueError("XPointNet: a spectrum's batch mixes is_optical flags; every image of one batch must go to the same encoder")
         return self._encoders["encoder_optical." if bool(f[0]) else "encoder_thermal."]
 
+    def forward_single(self, spectrum, seed=0, sample_ids=None):
+        """One spectrum's dict {'image' (B, 1, H, W), ['is_optical'], ...} (SyntheticShapes.load_batch's) -> the prediction dict `forward` builds
+        per spectrum ('logits', 'desc', detached 'encoder_output').  The batch goes to the encoder `_encoder_of` names (its `is_optical` flags when
+        multispectral), then to the heads.  sample_ids (B,) are the draw ids THEMSELVES (default 0 .. B - 1): `forward` on a pair batch is
+        forward_single(optical, seed, 2 ids) and forward_single(thermal, seed, 2 ids + 1), bit for bit.  The homography head takes no part."""
+        images = spectrum['image']
+        _need_device(images, "XPointNet")
+        n = images.shape[0]
+        ids = torch.arange(n) if sample_ids is None else torch.as_tensor(sample_ids).reshape(-1).cpu().to(torch.int64)
+        if ids.numel() != n:
+            raise ValueError(f"XPointNet: sample_ids must be ({n},)")
+        enc = self._encoder_of(spectrum, n)(images, seed=seed, sample_ids=ids)
+        pred = self._part["heads"]._forward(enc)
+        pred['encoder_output'] = enc.detach().permute(0, 3, 1, 2)
+        return pred
+
     def forward(self, data, seed=0, sample_ids=None):
         """data = {'optical': {'image' (B, 1, H, W), ['is_optical'], ...}, 'thermal': {...}} (augmentation.augment_pair_batch's dict) ->
         (pred_optical, pred_thermal, pred_hm), the reference's triple.  A prediction holds 'logits' (B, 65, H / 8, W / 8), 'desc' (B, D, H / 8, W / 8)
@@ -136,6 +152,22 @@ def train_step(model, data, loss_fn, optimizer, seed=0):
     if pred_hm is not None:
         loss_input['pred_hm'] = pred_hm
     loss, components = loss_fn(loss_input)
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), components
+
+
+def pretrain_step(model, data, loss_fn, optimizer, seed=0):
+    """`train_step` for a single-image batch (SyntheticShapes.load_batch's dict) and a loss with `descriptor_loss: false`: the detector's
+    pretraining step on synthetic shapes.  zero_grad, forward_single, loss, backward, optimizer.step; returns (loss, loss_components).  The
+    descriptor head exists (the reference's `descriptor_head: false` builds none) and receives ZERO gradients: under training.Adam with
+    weight_decay 0 its parameters and moments keep their bits."""
+    if loss_fn.config['descriptor_loss']:
+        raise ValueError("pretrain_step: the loss must be configured with 'descriptor_loss': False (a single image has no pair to describe)")
+    model.train()
+    optimizer.zero_grad(set_to_none=True)
+    pred = model.forward_single(data, seed=seed)
+    loss, components = loss_fn({'data': data, 'pred': pred})
     loss.backward()
     optimizer.step()
     return loss.detach(), components
