@@ -659,7 +659,8 @@ int xp_detector_loss_bwd(const float* logits, const int* labels, const float* va
  *     trunc((X / W, Y / W)) in f64, kept when inside after the truncation toward zero; kp_out is cleared first.  warp[b] == 0 copies.
  *   xp_aug_random_field: out (B, npix) f32, element p of field b from Philox4x32-10 with counter (p, 0, 0, seed >> 32) and key
  *     (seed & 0xffffffff, sample_ids[b] * 8 + primitive): XP_AUG_FIELD_UNIFORM (x0 >> 8) * 2^-24, XP_AUG_FIELD_NORMAL
- *     sqrt(-2 ln(1 - u0)) cos(2 pi u1).  sample_ids (B) int32 on the device, < 2^29.
+ *     sqrt(-2 ln(1 - u0)) cos(2 pi u1).  sample_ids (B) int32 on the device, < 2^29.  primitive: 0..8; 8 (XP_SYNTH_KEY_TEXTURE) has the key
+ *     of primitive 0 of sample id + 1: the texture of sample id and the Gaussian-noise field of sample id + 1 read one stream.
  *   xp_aug_photo_prologue: partials (B, xp_aug_partials_per_sample(H, W)) f64 partial sums of the images; shade (B, H, W) f32 or
  *     NULL: the 0/1 union of n_ellipses rotated ellipses per sample, ellipses (B, n_ellipses, 6) f64 = (cx, cy, a, b, cos, sin),
  *     inside iff ((dx cos + dy sin) / a)^2 + ((dy cos - dx sin) / b)^2 <= 1 in f64.
@@ -952,19 +953,43 @@ int xp_optim_adam_apply(float* const* params, const float* const* grads, const i
  *   xp_synth_resize: cv2.resize INTER_LINEAR (B, H, W) -> (B, h, w): source coordinate (d + 0.5) (H / h) - 0.5 in f64, taps clamped to the
  *     frame, f32 weights, rows first: (t00 (1 - wx) + t01 wx) (1 - wy) + (t10 (1 - wx) + t11 wx) wy.
  *   xp_synth_scatter_points: map (B, h, w) u8 = 0, then 1 at the first counts[b] (<= cap) points of points (B, cap, 2) int32 (y, x) that lie
- *     inside. */
+ *     inside.
+ *
+ * Textured polygons (draw_multiple_polygons; opt-in, a batch without a _TEXTURED record never reaches these two).  A _TEXTURED record is a
+ * _POLYGON record whose word 22 is the box-blur size k and whose word 23 is its ordinal j among the textured records of its image.  Its pixels
+ * take cv2.blur(T_j, (k, k)) (the definition of xp_synth_box_blur, reflected over the WHOLE frame), T_j(x, y) = the colour of the highest-index
+ * blob i < nb_blobs with dx^2 + dy^2 <= r^2, else the record's resolved colour; blob i of texture j of sample id is four uniforms
+ * u_c = the xp_aug_random_field uniform of (seed, id, XP_SYNTH_KEY_TEXTURE) at position (j nb_blobs + i) 4 + c: cx = floor(u0 W), cy = floor(u1 H),
+ * r = floor(u2 20) (products in f64), colour = f32(u3, or (u3 + 0.5) % 1 where u3 < min_contrast).  No blob list is ever stored.
+ *   xp_synth_texture: one JOB per textured record, work limited to the record's box dilated by the blur window.  jobs (n_jobs,
+ *     XP_SYNTH_JOB_INTS) int32 = image b, record r, ordinal j, k, the record's box x0 y0 x1 y1 (inclusive, inside the frame), the texture box
+ *     tx0 ty0 tx1 ty1 = the hull of the frame positions that the windows of the record's box reach after reflection, 4 spare.  offsets
+ *     (n_jobs, 3) int64 = where, in floats from `arena`, the job keeps T_j over its texture box (th x tw), the row pass (th x bw) and the blurred
+ *     box (bh x bw); a job whose extents leave the frame or the arena (arena_floats) is skipped.  units (3, n_jobs + 1) int32 = per launch the
+ *     running count of workgroups before each job: 32 x 32 tiles of the texture box; rows of the texture box; 64-column by 256-row blocks of the
+ *     record's box.  Three launches whatever B and n_jobs: the texture (blobs culled per tile in index order, the list holds all nb_blobs), the
+ *     row windows (f64 prefix over the frame's row, zero outside the texture box), the column windows (f64 running sums).  min_ksize, max_ksize:
+ *     the range of k over the jobs, inside [1, 500]; nb_blobs <= XP_SYNTH_MAX_TEXTURE_BLOBS.  n_tiles, n_rows, n_col_blocks: the last entry of
+ *     each row of units, the three grids.
+ *   xp_synth_rasterise_textured: xp_synth_rasterise with one more kind: a pixel inside a _TEXTURED record r of image b (the _POLYGON test) takes
+ *     arena[tex_offsets[b][r] + (y - y0) bw + (x - x0)], the job's blurred box; tex_offsets (B, n_records) int64, negative = draws nothing. */
 #define XP_SYNTH_PARTIALS 128
 #define XP_SYNTH_MAX_RECORDS 128
 #define XP_SYNTH_RECORD_INTS 24
 #define XP_SYNTH_CANDIDATES 21
 #define XP_SYNTH_KEY_BACKGROUND 6
 #define XP_SYNTH_KEY_NOISE 7
+#define XP_SYNTH_KEY_TEXTURE 8
+#define XP_SYNTH_MAX_TEXTURE_BLOBS 4096
+#define XP_SYNTH_MAX_KSIZE 500
+#define XP_SYNTH_JOB_INTS 16
 #define XP_SYNTH_NOP 0
 #define XP_SYNTH_CIRCLE 1
 #define XP_SYNTH_SEGMENT 2
 #define XP_SYNTH_POLYGON 3
 #define XP_SYNTH_ELLIPSE 4
 #define XP_SYNTH_NOISE 5
+#define XP_SYNTH_TEXTURED 6
 #define XP_SYNTH_RULE_ABS 0
 #define XP_SYNTH_RULE_CONTRAST 1
 #define XP_SYNTH_RULE_DIFFERENT 2
@@ -979,6 +1004,11 @@ int xp_synth_rasterise(float* frame, const int* records, const float* colours, u
                        int B, int H, int W, void* stream);
 int xp_synth_resize(const float* src, float* dst, int B, int H, int W, int h, int w, void* stream);
 int xp_synth_scatter_points(const int* points, const int* counts, int cap, uint8_t* map, int B, int h, int w, void* stream);
+int xp_synth_texture(float* arena, long long arena_floats, const int* jobs, const long long* offsets, const int* units, int n_jobs,
+                     const float* colours, int n_records, unsigned long long seed, const int* sample_ids, int nb_blobs, double min_contrast,
+                     int min_ksize, int max_ksize, int n_tiles, int n_rows, int n_col_blocks, int B, int H, int W, void* stream);
+int xp_synth_rasterise_textured(float* frame, const int* records, const float* colours, unsigned long long seed, const int* sample_ids,
+                                const float* arena, const long long* tex_offsets, int n_records, int B, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; replaces the

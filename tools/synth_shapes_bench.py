@@ -7,7 +7,10 @@ of 32 only, so the reference's 240 rows become 256: the step's batch is generate
 Per case one JSON line: host ms per batch (`sample_draw_lists` + `pack_draw_lists`, a host clock; fresh indices every batch), device ms per
 batch (`render` between device events, after a warm-up: the uploads of the tables are part of a batch), kernel launches per batch (DERIVED, not
 counted: the entry-point calls of the xp_prof_* rows times the kernels each entry point launches, a table kept in this file) and images / s
-of the slower of the two sides; every time as median [min, max] over `--runs` windows of `--reps` batches.  Then the
+of the slower of the two sides; every time as median [min, max] over `--runs` windows of `--reps` batches.  After the eight primitives and
+their 'all', the same for draw_multiple_polygons alone and for the 'all' of nine (the dataset key textured_polygons), with the arena of the
+texture jobs (MiB per batch) and the three texture launches' own time (the xp_prof_* row of xp_synth_texture, a run with the event timing on)
+against their algorithmic bytes: every float of the arena written once and read once.  Then the
 pretrain step's ms the same way, the sentence that matters (is a batch generated in less time than it is consumed, host side and device side
 separately), and, for context, the CPU seconds per image of the numpy restatement (tests/synthetic_shapes_f64.py) on this machine: that is
 NOT the reference's time (OpenCV is not installed; its generator cannot run here)."""
@@ -34,8 +37,8 @@ def spread(v):
     return {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
 
 
-def bench_case(primitives, runs, reps, first_index):
-    cfg = ss.merge_config({'primitives': primitives, 'generation_size': GEN, 'image_size': IMG})
+def bench_case(primitives, runs, reps, first_index, textured=False):
+    cfg = ss.merge_config({'primitives': primitives, 'textured_polygons': textured, 'generation_size': GEN, 'image_size': IMG})
     host, device = [], []
     index = first_index
 
@@ -50,13 +53,17 @@ def bench_case(primitives, runs, reps, first_index):
     ss.render(tables, GEN, IMG, 1, DEV)                                   # warm-up: code objects, allocator
     rows = aug.profile_launches(lambda: ss.render(tables, GEN, IMG, 1, DEV))
     two = ("synth_background", "synth_box_blur", "synth_resolve_colours")  # entry points that launch two kernels; every other one launches one
-    launches = int(sum(r[0] * (2 if tag in two else 1) for tag, r in rows.items()))
+    launches = int(sum(r[0] * (3 if tag == "synth_texture" else 2 if tag in two else 1) for tag, r in rows.items()))
+    arena = []
     for _ in range(runs):
         h, batches = [], []
         for _ in range(reps):
             tables, ms = batch()
             h.append(ms)
             batches.append(tables)
+            if textured:
+                jobs = ss.texture_jobs(tables, GEN)
+                arena.append(jobs['arena_floats'] * 4 / 2 ** 20 if jobs else 0.0)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -67,8 +74,17 @@ def bench_case(primitives, runs, reps, first_index):
         host.append(sum(h) / reps)
         device.append(e0.elapsed_time(e1) / reps)
     slower = max(statistics.median(host), statistics.median(device))
-    return {"primitives": primitives, "batch": B, "host_ms_per_batch": spread(host), "device_ms_per_batch": spread(device),
-            "kernel_launches_per_batch_derived": launches, "images_per_s": round(B / slower * 1e3, 1)}
+    row = {"primitives": primitives, "batch": B, "host_ms_per_batch": spread(host), "device_ms_per_batch": spread(device),
+           "kernel_launches_per_batch_derived": launches, "images_per_s": round(B / slower * 1e3, 1)}
+    if textured:
+        row["textured_polygons"] = True
+        row["texture_arena_mib_per_batch"] = spread(arena)
+        tex = [aug.profile_launches(lambda: ss.render(t, GEN, IMG, 1, DEV)).get("synth_texture") for t in batches]
+        tex = [t for t in tex if t]
+        if tex:          # (calls, ms, algorithmic bytes) of the three texture launches of one batch
+            row["texture_launches_ms"] = spread([t[1] for t in tex])
+            row["texture_launches_gb_per_s"] = spread([t[2] / (t[1] * 1e-3) / 1e9 for t in tex])
+    return row
 
 
 def bench_pretrain(runs, steps):
@@ -122,13 +138,17 @@ def main():
     for k, prims in enumerate([[p] for p in ss.IMPLEMENTED] + ['all']):
         rows.append(bench_case(prims, args.runs, args.reps, first_index=100000 * k))
         print(json.dumps(rows[-1]), flush=True)
+    for k, prims in enumerate([['draw_multiple_polygons'], 'all']):
+        rows.append(bench_case(prims, args.runs, args.reps, first_index=100000 * (len(ss.ALL_PRIMITIVES) + k), textured=True))
+        print(json.dumps(rows[-1]), flush=True)
     step = bench_pretrain(args.runs, args.steps)
     print(json.dumps(step), flush=True)
-    gen, ms = rows[-1], step["pretrain_step_ms"]["median"]
-    for side in ("host", "device"):
-        g = gen[f"{side}_ms_per_batch"]["median"]
-        print(f"# 'all': the {side} side generates a batch in {g:.1f} ms, one pretrain_step consumes it in {ms:.1f} ms: generation is "
-              f"{'FASTER' if g < ms else 'SLOWER'} than consumption on the {side} side ({g / ms:.2f} x)")
+    ms = step["pretrain_step_ms"]["median"]
+    for name, gen in (("'all' of eight", rows[len(ss.IMPLEMENTED)]), ("'all' of nine (textured_polygons)", rows[-1])):
+        for side in ("host", "device"):
+            g = gen[f"{side}_ms_per_batch"]["median"]
+            print(f"# {name}: the {side} side generates a batch in {g:.1f} ms, one pretrain_step consumes it in {ms:.1f} ms: generation is "
+                  f"{'FASTER' if g < ms else 'SLOWER'} than consumption on the {side} side ({g / ms:.2f} x)")
     if args.restatement_images > 0:
         sec, prims = restatement_seconds(args.restatement_images)
         print(f"# numpy restatement (tests/synthetic_shapes_f64.py) on this machine's CPU: {sec:.2f} s per image ({prims}); NOT the reference's time")

@@ -163,6 +163,8 @@ _SIGNATURES = {
     "xp_synth_box_blur": [c_p] * 4 + [c_i] * 3 + [c_p],
     "xp_synth_resolve_colours": [c_p] * 4 + [c_i, c_i] + [c_p] * 3 + [c_i] * 3 + [c_p],
     "xp_synth_rasterise": [c_p, c_p, c_p, ctypes.c_uint64, c_p] + [c_i] * 4 + [c_p],
+    "xp_synth_texture": [c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_i, c_d] + [c_i] * 8 + [c_p],
+    "xp_synth_rasterise_textured": [c_p, c_p, c_p, ctypes.c_uint64, c_p, c_p, c_p] + [c_i] * 4 + [c_p],
     "xp_synth_resize": [c_p, c_p] + [c_i] * 5 + [c_p],
     "xp_synth_scatter_points": [c_p, c_p, c_i, c_p] + [c_i] * 3 + [c_p],
     "xp_prof_enable": [c_i],

@@ -7,11 +7,12 @@
                                        [-i 0] [-n all] [-s 0] [--chunk K]
     python -m xpoint_amd.cli train     -y configs/cmt.yaml [-w <output_directory>/e20.model] [-s 0]
     python -m xpoint_amd.cli benchmark -y configs/cipdp.yaml -m model_weights/XPoint-EXP1 -v latest [-s 0] [-o out.json]
-    python -m xpoint_amd.cli synth     -y configs/config_synthetic_shapes.yaml -n 16 -o shapes.npz [-i 0] [-s 0]
+    python -m xpoint_amd.cli synth     -y configs/config_synthetic_shapes.yaml -n 16 -o shapes.npz [-i 0] [-s 0] [--textured-polygons]
 
 `synth` is show_synthetic_images.py without the plots: samples -i .. -i + n - 1 of the SyntheticShapes dataset of the YAML's `dataset:` block
 (xpoint_amd.synthetic_shapes: rendered on the GPU, then augmented as the block says), written to -o as image (n, 1, h, w) f32, keypoints
 (n, h, w) bool, valid_mask (n, 1, h, w) bool and is_optical (n, 1) bool.  Sample i depends on (-s, i) alone.  -m, -v are not used.
+--textured-polygons sets the block's `textured_polygons: true`: draw_multiple_polygons is accepted and `primitives: 'all'` means all nine.
 
 `benchmark` is the -e half of benchmark.py:175-249 (see `benchmark`): repeatability, NN-mAP, M-score and homography correctness over the WHOLE
 folder dataset in batches of prediction.batchsize (evaluation.compute_metrics_batched), with the script's threshold lists (1..10 for the
@@ -249,6 +250,7 @@ def build_parser():
     ap.add_argument('-o', '--output', default=None, help='write keypoints / matches of the samples to this .npz (benchmark: the result JSON; synth: the samples)')
     ap.add_argument('--chunk', default=None, type=int, help='export: homographies per forward (does not change the result)')
     ap.add_argument('-w', '--weight-file', default=None, help='train: file containing the weights to initialize the weights (e<N>.model resumes at epoch N)')
+    ap.add_argument('--textured-polygons', action='store_true', help="synth: set the dataset's textured_polygons key (draw_multiple_polygons; 'all' = the nine primitives)")
     ap.add_argument('--device', default='cuda:0')
     return ap
 
@@ -335,6 +337,8 @@ def synth_shapes(args):
     if ds.get('type', 'SyntheticShapes') != 'SyntheticShapes':
         raise SystemExit(f"synth: dataset.type must be 'SyntheticShapes', got {ds.get('type')!r}")
     ds.pop('type', None)
+    if args.textured_polygons:
+        ds['textured_polygons'] = True
     if not torch.cuda.is_available():
         raise SystemExit("xpoint_amd runs on the GPU only (no CPU fallback)")
     from . import synthetic_shapes

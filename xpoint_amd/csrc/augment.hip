@@ -246,7 +246,8 @@ extern "C" int xp_aug_scatter_labels(const uint8_t* kp_in, uint8_t* kp_out, cons
 extern "C" int xp_aug_random_field(float* out, unsigned long long seed, const int* sample_ids, int primitive, int kind, int B, int npix, void* stream) {
     XP_CHECK_ARG(out && sample_ids, "xp_aug_random_field: null pointer");
     XP_CHECK_ARG(B > 0 && B <= 65535 && npix > 0 && npix <= (1 << 30), "xp_aug_random_field: bad shape (%d fields of %d)", B, npix);
-    XP_CHECK_ARG(primitive >= 0 && primitive < 8, "xp_aug_random_field: primitive must be 0..7, got %d", primitive);
+    XP_CHECK_ARG(primitive >= 0 && primitive <= XP_SYNTH_KEY_TEXTURE, "xp_aug_random_field: primitive must be 0..%d, got %d", XP_SYNTH_KEY_TEXTURE,
+                 primitive);
     XP_CHECK_ARG(kind == XP_AUG_FIELD_UNIFORM || kind == XP_AUG_FIELD_NORMAL, "xp_aug_random_field: unknown kind %d", kind);
     const dim3 grid(xp_cdiv(npix, AUG_BLOCK), B), block(AUG_BLOCK);
     XpProfScope prof("aug_random_field", (hipStream_t)stream, 0.0, 4.0 * B * npix);

@@ -13,6 +13,11 @@
 //   xp_synth_resolve_colours  f64 partial sums of the blurred background in a fixed order, then one thread per image walks the colour rules.
 //   xp_synth_rasterise        one thread per pixel, the image's records in LDS, bounding box first, the last covering record wins.  Integer
 //                             inside tests (64-bit); the ellipse alone is f64, evaluated as written (-ffp-contract=off).
+//   xp_synth_texture          draw_multiple_polygons' textures, one job per textured record, three launches for any batch: T_j on the job's texture
+//                             box (the blobs come out of Philox per 32 x 32 tile, culled, kept in index order), then the box blur's two passes
+//                             restricted to what the record's box needs.  The host lays the jobs out in one arena and gives every launch a table
+//                             of running workgroup counts; a workgroup finds its job by bisection.
+//   xp_synth_rasterise_textured  the rasteriser with the TEXTURED kind: such a polygon's pixels are read from its job's blurred box.
 //   xp_synth_resize           cv2.resize INTER_LINEAR: source coordinate (d + 0.5) scale - 0.5, clamped taps, f32 weights.
 //   xp_synth_scatter_points   the keypoint map from the host's integer points: the constant byte 1, collisions are benign.
 #include "cv_geom.h"
@@ -97,6 +102,49 @@ __device__ __forceinline__ double sy_ext_prefix(const double* __restrict__ P, in
     return (double)q * sp + part;
 }
 
+// the row s_p[0 .. W) in LDS becomes its inclusive f64 prefix, in a fixed order: per-thread chunks, then the 256 chunk totals in ascending order.
+// Every thread of the block calls it after the barrier that follows the load; it ends on a barrier.
+__device__ __forceinline__ void sy_row_prefix(double* __restrict__ s_p, double* __restrict__ s_part, int W) {
+    const int t = threadIdx.x, C = (W + 255) / 256, i0 = t * C, i1 = min(i0 + C, W);
+    double acc = 0.0;
+    for (int i = i0; i < i1; ++i) { acc = acc + s_p[i]; s_p[i] = acc; }
+    s_part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double run = 0.0;
+        for (int k = 0; k < 256; ++k) { const double c = s_part[k]; s_part[k] = run; run = run + c; }
+    }
+    __syncthreads();
+    const double base = s_part[t];
+    for (int i = i0; i < i1; ++i) s_p[i] = base + s_p[i];
+    __syncthreads();
+}
+
+// the sum of the row's reflected extension over the window [x - a, x - a + ks - 1], from the row's prefix
+__device__ __forceinline__ double sy_row_window(const double* __restrict__ s_p, int W, int x, int a, int ks) {
+    if (W == 1) return (double)ks * s_p[0];
+    const int lo = x - a, hi = x - a + ks - 1;
+    double sum = sy_ext_prefix(s_p, W, hi);
+    if (lo > 0) sum = sum - sy_ext_prefix(s_p, W, lo - 1);
+    else if (lo < 0) sum = sum + (sy_ext_prefix(s_p, W, -lo) - s_p[0]);          // E is even about 0
+    return sum;
+}
+
+// one lane's column windows of the rows y0 .. y1 - 1: an f64 running sum started from a direct sum.  load(i): the column at frame row i in [0, H)
+template <typename Load, typename Store>
+__device__ __forceinline__ void sy_col_windows(Load load, Store store, int y0, int y1, int ks, int H) {
+    const int a = ks / 2;
+    const double inv = (double)ks;
+    double run = 0.0;
+    for (int i = y0 - a; i <= y0 - a + ks - 1; ++i) run = run + (double)load(xp_cv_reflect101(i, H));
+    store(y0, (float)(run / inv));
+    for (int y = y0 + 1; y < y1; ++y) {
+        run = run + (double)load(xp_cv_reflect101(y - a + ks - 1, H));
+        run = run - (double)load(xp_cv_reflect101(y - 1 - a, H));
+        store(y, (float)(run / inv));
+    }
+}
+
 // grid (H, B): one block per row
 __global__ __launch_bounds__(256) void synth_box_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ ksizes,
                                                              int H, int W) {
@@ -106,34 +154,11 @@ __global__ __launch_bounds__(256) void synth_box_rows_kernel(const float* __rest
     const float* s = src + ((size_t)b * H + y) * W;
     float* d = dst + ((size_t)b * H + y) * W;
     const int ks = max(ksizes[b], 1), a = ks / 2;
-    const int C = (W + 255) / 256, i0 = t * C, i1 = min(i0 + C, W);
     for (int i = t; i < W; i += 256) s_p[i] = (double)s[i];          // consecutive lanes on consecutive pixels
     __syncthreads();
-    double acc = 0.0;
-    for (int i = i0; i < i1; ++i) { acc = acc + s_p[i]; s_p[i] = acc; }
-    s_part[t] = acc;
-    __syncthreads();
-    if (t == 0) {                                     // 256 chunk totals in ascending order: the fixed order of the row's prefix
-        double run = 0.0;
-        for (int k = 0; k < 256; ++k) { const double c = s_part[k]; s_part[k] = run; run = run + c; }
-    }
-    __syncthreads();
-    const double base = s_part[t];
-    for (int i = i0; i < i1; ++i) s_p[i] = base + s_p[i];
-    __syncthreads();
+    sy_row_prefix(s_p, s_part, W);
     const double inv = (double)ks;
-    for (int x = t; x < W; x += 256) {
-        double sum;
-        if (W == 1) {
-            sum = (double)ks * s_p[0];
-        } else {
-            const int lo = x - a, hi = x - a + ks - 1;
-            sum = sy_ext_prefix(s_p, W, hi);
-            if (lo > 0) sum = sum - sy_ext_prefix(s_p, W, lo - 1);
-            else if (lo < 0) sum = sum + (sy_ext_prefix(s_p, W, -lo) - s_p[0]);          // E is even about 0
-        }
-        d[x] = (float)(sum / inv);
-    }
+    for (int x = t; x < W; x += 256) d[x] = (float)(sy_row_window(s_p, W, x, a, ks) / inv);
 }
 
 // grid (ceil(W / 64), ceil(H / (4 SY_VSEG)), B): lane = column, the block's 4 waves take 4 consecutive row segments
@@ -144,16 +169,7 @@ __global__ __launch_bounds__(256) void synth_box_cols_kernel(const float* __rest
     if (x >= W || y0 >= H) return;
     const float* s = src + (size_t)b * H * W + x;
     float* d = dst + (size_t)b * H * W + x;
-    const int ks = max(ksizes[b], 1), a = ks / 2;
-    const double inv = (double)ks;
-    double run = 0.0;
-    for (int i = y0 - a; i <= y0 - a + ks - 1; ++i) run = run + (double)s[(size_t)xp_cv_reflect101(i, H) * W];
-    d[(size_t)y0 * W] = (float)(run / inv);
-    for (int y = y0 + 1; y < y1; ++y) {
-        run = run + (double)s[(size_t)xp_cv_reflect101(y - a + ks - 1, H) * W];
-        run = run - (double)s[(size_t)xp_cv_reflect101(y - 1 - a, H) * W];
-        d[(size_t)y * W] = (float)(run / inv);
-    }
+    sy_col_windows([&](int i) { return s[(size_t)i * W]; }, [&](int y, float v) { d[(size_t)y * W] = v; }, y0, y1, max(ksizes[b], 1), H);
 }
 
 // grid (SY_PART, B): f64 partial sums in a fixed order
@@ -231,8 +247,12 @@ __device__ __forceinline__ bool sy_in_ellipse(int px, int py, const int* g) {
 }
 
 // records (B, R, SY_REC) int32: kind, bbox x0 y0 x1 y1 (inclusive), n (radius / thickness / vertex count), 16 geometry words, 2 spare
+// TEX: the list may hold XP_SYNTH_TEXTURED records, polygons whose pixels come from the blurred box of their job (arena + tex_off[b][r], rows of
+// the bbox's width) instead of a colour; without TEX the two tables are not read.
+template <bool TEX>
 __global__ __launch_bounds__(256) void synth_raster_kernel(float* __restrict__ frame, const int* __restrict__ records, const float* __restrict__ colours,
-                                                           uint64_t seed, const int* __restrict__ ids, int R, int H, int W) {
+                                                           uint64_t seed, const int* __restrict__ ids, const float* __restrict__ arena,
+                                                           const long long* __restrict__ tex_off, int R, int H, int W) {
     __shared__ __attribute__((aligned(8))) int s_rec[SY_MAX_REC * SY_REC];
     __shared__ float s_col[SY_MAX_REC];
     const int b = blockIdx.z;
@@ -257,13 +277,158 @@ __global__ __launch_bounds__(256) void synth_raster_kernel(float* __restrict__ f
             in = dx * dx + dy * dy <= rr * rr;
         } else if (kind == XP_SYNTH_SEGMENT) {
             in = sy_in_segment(x, y, g, q[5]);
-        } else if (kind == XP_SYNTH_POLYGON) {
+        } else if (kind == XP_SYNTH_POLYGON || (TEX && kind == XP_SYNTH_TEXTURED)) {
             in = sy_in_polygon(x, y, g, min(max(q[5], 0), 8));
         } else if (kind == XP_SYNTH_ELLIPSE) {
             in = sy_in_ellipse(x, y, g);
         }
+        if (TEX && in && kind == XP_SYNTH_TEXTURED) {
+            const long long off = tex_off[(size_t)b * R + r];
+            if (off < 0) continue;          // a record without a job draws nothing
+            frame[((size_t)b * H + y) * W + x] = arena[off + (long long)(y - q[2]) * (q[3] - q[1] + 1) + (x - q[1])];
+            return;
+        }
         if (in) { frame[((size_t)b * H + y) * W + x] = s_col[r]; return; }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- textured polygons
+constexpr int SY_TEX_BLOBS = XP_SYNTH_MAX_TEXTURE_BLOBS;
+constexpr int SY_TEX_TILE = 32;                 // the texture launch culls the blobs once per 32 x 32 tile
+constexpr int SY_JOB = XP_SYNTH_JOB_INTS;
+
+// one textured record's work item: see xp_synth_texture in include/xpoint_hip.h
+struct SyJob {
+    int b, r, j, ks, x0, y0, x1, y1, tx0, ty0, tx1, ty1, unit;      // unit: this workgroup's index among the job's
+    long long off_tex, off_rows, off_out;
+    bool ok;
+    __device__ __forceinline__ int bw() const { return x1 - x0 + 1; }
+    __device__ __forceinline__ int bh() const { return y1 - y0 + 1; }
+    __device__ __forceinline__ int tw() const { return tx1 - tx0 + 1; }
+    __device__ __forceinline__ int th() const { return ty1 - ty0 + 1; }
+};
+
+// the job of workgroup `wg` of one launch: units (n_jobs + 1) is that launch's running count of workgroups, so the job is the last one that
+// starts at or before wg.  ok = every extent lies inside the frame and the arena; a workgroup of a job that is not ok does nothing.
+__device__ __forceinline__ SyJob sy_job_of(const int* __restrict__ jobs, const long long* __restrict__ offsets, const int* __restrict__ units,
+                                           int n_jobs, int wg, long long arena_floats, int B, int R, int H, int W) {
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (units[mid] <= wg) lo = mid; else hi = mid - 1;
+    }
+    const int* q = jobs + (size_t)lo * SY_JOB;
+    SyJob j;
+    j.b = q[0]; j.r = q[1]; j.j = q[2]; j.ks = min(max(q[3], 1), XP_SYNTH_MAX_KSIZE);
+    j.x0 = q[4]; j.y0 = q[5]; j.x1 = q[6]; j.y1 = q[7]; j.tx0 = q[8]; j.ty0 = q[9]; j.tx1 = q[10]; j.ty1 = q[11];
+    j.unit = wg - units[lo];
+    j.off_tex = offsets[(size_t)lo * 3]; j.off_rows = offsets[(size_t)lo * 3 + 1]; j.off_out = offsets[(size_t)lo * 3 + 2];
+    j.ok = j.b >= 0 && j.b < B && j.r >= 0 && j.r < R && j.j >= 0 && j.j < SY_MAX_REC && j.unit >= 0 &&
+           0 <= j.tx0 && j.tx0 <= j.x0 && j.x0 <= j.x1 && j.x1 <= j.tx1 && j.tx1 < W &&
+           0 <= j.ty0 && j.ty0 <= j.y0 && j.y0 <= j.y1 && j.y1 <= j.ty1 && j.ty1 < H &&
+           j.off_tex >= 0 && j.off_tex + (long long)j.tw() * j.th() <= arena_floats &&
+           j.off_rows >= 0 && j.off_rows + (long long)j.bw() * j.th() <= arena_floats &&
+           j.off_out >= 0 && j.off_out + (long long)j.bw() * j.bh() <= arena_floats;
+    return j;
+}
+
+__device__ __forceinline__ float sy_tex_uniform(uint64_t seed, int id, int j, int NB, int i, int c) {
+    return aug_uniform(aug_philox(seed, (uint32_t)id, XP_SYNTH_KEY_TEXTURE, (uint32_t)((j * NB + i) * 4 + c)).x);
+}
+
+// grid (tiles of every job): T_j over one 32 x 32 tile of the job's texture box.  The blobs come out of Philox here: thread t decodes the blobs
+// t C .. t C + C - 1 (C = ceil(NB / 256)), keeps those whose disc reaches the tile, and an ordered compaction (a scan of the 256 counts) leaves
+// the survivors in index order, so "the highest index wins" is the first hit of a walk from the list's end.  The list holds all NB blobs: on a
+// small frame every blob reaches every tile.  Only the winner's colour is drawn.  A blob is packed as cx | cy << 12 | r << 24 (cx, cy < 4096, r < 20).
+__global__ __launch_bounds__(256) void synth_texture_kernel(float* __restrict__ arena, long long arena_floats, const int* __restrict__ jobs,
+                                                            const long long* __restrict__ offsets, const int* __restrict__ units, int n_jobs,
+                                                            const float* __restrict__ colours, int R, uint64_t seed, const int* __restrict__ ids,
+                                                            int NB, double mc, int B, int H, int W) {
+    __shared__ uint32_t s_raw[SY_TEX_BLOBS];
+    __shared__ uint32_t s_list[SY_TEX_BLOBS];
+    __shared__ uint16_t s_idx[SY_TEX_BLOBS];
+    __shared__ int s_cnt[257];
+    const SyJob jb = sy_job_of(jobs, offsets, units, n_jobs, blockIdx.x, arena_floats, B, R, H, W);
+    if (!jb.ok) return;
+    const int t = threadIdx.x, tw = jb.tw(), tiles_x = (tw + SY_TEX_TILE - 1) / SY_TEX_TILE;
+    const int ox = jb.tx0 + (jb.unit % tiles_x) * SY_TEX_TILE, oy = jb.ty0 + (jb.unit / tiles_x) * SY_TEX_TILE;
+    if (oy > jb.ty1) return;
+    const int ex = min(ox + SY_TEX_TILE - 1, jb.tx1), ey = min(oy + SY_TEX_TILE - 1, jb.ty1);
+    const int id = ids[jb.b];
+    const int C = (NB + 255) / 256, i0 = t * C, i1 = min(i0 + C, NB);
+    int cnt = 0;
+    for (int i = i0; i < i1; ++i) {
+        const int cx = (int)floor((double)sy_tex_uniform(seed, id, jb.j, NB, i, 0) * (double)W);
+        const int cy = (int)floor((double)sy_tex_uniform(seed, id, jb.j, NB, i, 1) * (double)H);
+        const int rr = (int)floor((double)sy_tex_uniform(seed, id, jb.j, NB, i, 2) * 20.0);
+        const int dx = max(max(ox - cx, cx - ex), 0), dy = max(max(oy - cy, cy - ey), 0);          // to the nearest pixel of the tile
+        const bool keep = dx * dx + dy * dy <= rr * rr;
+        s_raw[i] = keep ? ((uint32_t)cx | ((uint32_t)cy << 12) | ((uint32_t)rr << 24)) : 0xFFFFFFFFu;
+        cnt += keep ? 1 : 0;
+    }
+    s_cnt[t] = cnt;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < 256; ++k) { const int c = s_cnt[k]; s_cnt[k] = run; run += c; }
+        s_cnt[256] = run;
+    }
+    __syncthreads();
+    int pos = s_cnt[t];
+    for (int i = i0; i < i1; ++i) {
+        const uint32_t g = s_raw[i];
+        if (g != 0xFFFFFFFFu) { s_list[pos] = g; s_idx[pos] = (uint16_t)i; ++pos; }
+    }
+    __syncthreads();
+    const int n = s_cnt[256];
+    const float base = colours[(size_t)jb.b * R + jb.r];
+    const int px = ox + (t & 31);
+    if (px > ex) return;
+    for (int py = oy + (t >> 5); py <= ey; py += 8) {
+        int win = -1;
+        for (int m = n - 1; m >= 0; --m) {
+            const uint32_t g = s_list[m];
+            const int dx = px - (int)(g & 0xFFFu), dy = py - (int)((g >> 12) & 0xFFFu), rr = (int)(g >> 24);
+            if (dx * dx + dy * dy <= rr * rr) { win = s_idx[m]; break; }
+        }
+        const float v = win < 0 ? base : (float)sy_contrast((double)sy_tex_uniform(seed, id, jb.j, NB, win, 3), 0.0, mc);
+        arena[jb.off_tex + (long long)(py - jb.ty0) * tw + (px - jb.tx0)] = v;
+    }
+}
+
+// grid (rows of every job's texture box): the row windows of the columns x0 .. x1.  The row is laid over the frame's width, zero outside the
+// texture box (no window of the record's box reaches there), so the prefix and the reflection are those of the whole-frame blur.
+__global__ __launch_bounds__(256) void synth_texture_rows_kernel(float* __restrict__ arena, long long arena_floats, const int* __restrict__ jobs,
+                                                                 const long long* __restrict__ offsets, const int* __restrict__ units, int n_jobs,
+                                                                 int B, int R, int H, int W) {
+    __shared__ double s_p[SY_MAX_W];
+    __shared__ double s_part[256];
+    const SyJob jb = sy_job_of(jobs, offsets, units, n_jobs, blockIdx.x, arena_floats, B, R, H, W);
+    if (!jb.ok || jb.unit >= jb.th()) return;
+    const int t = threadIdx.x, tw = jb.tw(), bw = jb.bw();
+    const float* s = arena + jb.off_tex + (long long)jb.unit * tw;
+    float* d = arena + jb.off_rows + (long long)jb.unit * bw;
+    for (int i = t; i < W; i += 256) s_p[i] = (i >= jb.tx0 && i <= jb.tx1) ? (double)s[i - jb.tx0] : 0.0;
+    __syncthreads();
+    sy_row_prefix(s_p, s_part, W);
+    const double inv = (double)jb.ks;
+    for (int x = jb.x0 + t; x <= jb.x1; x += 256) d[x - jb.x0] = (float)(sy_row_window(s_p, W, x, jb.ks / 2, jb.ks) / inv);
+}
+
+// grid (64-column x 4 SY_VSEG-row blocks of every job's box): lane = column, the block's 4 waves take 4 consecutive row segments
+__global__ __launch_bounds__(256) void synth_texture_cols_kernel(float* __restrict__ arena, long long arena_floats, const int* __restrict__ jobs,
+                                                                 const long long* __restrict__ offsets, const int* __restrict__ units, int n_jobs,
+                                                                 int B, int R, int H, int W) {
+    const SyJob jb = sy_job_of(jobs, offsets, units, n_jobs, blockIdx.x, arena_floats, B, R, H, W);
+    if (!jb.ok) return;
+    const int bw = jb.bw(), blocks_x = (bw + 63) / 64;
+    const int x = (jb.unit % blocks_x) * 64 + (threadIdx.x & 63);                                  // relative to x0
+    const int y0 = jb.y0 + ((jb.unit / blocks_x) * 4 + (threadIdx.x >> 6)) * SY_VSEG, y1 = min(y0 + SY_VSEG, jb.y1 + 1);
+    if (x >= bw || y0 > jb.y1) return;
+    const float* s = arena + jb.off_rows + x;
+    float* d = arena + jb.off_out + x;
+    sy_col_windows([&](int i) { return s[(long long)(min(max(i, jb.ty0), jb.ty1) - jb.ty0) * bw]; },
+                   [&](int y, float v) { d[(long long)(y - jb.y0) * bw] = v; }, y0, y1, jb.ks, H);
 }
 
 __device__ __forceinline__ void sy_resize_tap(int d, double scale, int n, int& i0, int& i1, float& w) {
@@ -368,8 +533,51 @@ extern "C" int xp_synth_rasterise(float* frame, const int* records, const float*
     SY_NOT_NULL(frame); SY_NOT_NULL(records); SY_NOT_NULL(colours); SY_NOT_NULL(sample_ids);
     SY_ALIGNED8(records);
     XpProfScope prof("synth_rasterise", (hipStream_t)stream, 0.0, 8.0 * B * H * W);
-    hipLaunchKernelGGL(synth_raster_kernel, xp_tile_grid(W, H, B), dim3(256), 0, (hipStream_t)stream, frame, records, colours, (uint64_t)seed, sample_ids,
-                       n_records, H, W);
+    hipLaunchKernelGGL(synth_raster_kernel<false>, xp_tile_grid(W, H, B), dim3(256), 0, (hipStream_t)stream, frame, records, colours, (uint64_t)seed,
+                       sample_ids, (const float*)nullptr, (const long long*)nullptr, n_records, H, W);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+extern "C" int xp_synth_texture(float* arena, long long arena_floats, const int* jobs, const long long* offsets, const int* units, int n_jobs,
+                                const float* colours, int n_records, unsigned long long seed, const int* sample_ids, int nb_blobs, double min_contrast,
+                                int min_ksize, int max_ksize, int n_tiles, int n_rows, int n_col_blocks, int B, int H, int W, void* stream) {
+    const char* fn = "xp_synth_texture";
+    if (int rc = sy_check_frame(fn, B, H, W)) return rc;
+    XP_CHECK_ARG(n_jobs >= 1 && n_jobs <= B * SY_MAX_REC, "%s: n_jobs must be in [1, B * %d] (got %d)", fn, SY_MAX_REC, n_jobs);
+    XP_CHECK_ARG(n_records >= 1 && n_records <= SY_MAX_REC, "%s: n_records must be in [1, %d] (got %d)", fn, SY_MAX_REC, n_records);
+    XP_CHECK_ARG(nb_blobs >= 0 && nb_blobs <= SY_TEX_BLOBS, "%s: nb_blobs must be in [0, %d] (got %d)", fn, SY_TEX_BLOBS, nb_blobs);
+    XP_CHECK_ARG(min_contrast >= 0.0 && min_contrast <= 1.0, "%s: min_contrast must be in [0, 1] (got %g)", fn, min_contrast);
+    XP_CHECK_ARG(min_ksize >= 1 && min_ksize <= max_ksize && max_ksize <= XP_SYNTH_MAX_KSIZE, "%s: ksize must be in [1, %d] (got %d .. %d)", fn,
+                 XP_SYNTH_MAX_KSIZE, min_ksize, max_ksize);
+    XP_CHECK_ARG(arena_floats >= 1, "%s: arena_floats must be positive (got %lld)", fn, arena_floats);
+    SY_NOT_NULL(arena); SY_NOT_NULL(jobs); SY_NOT_NULL(offsets); SY_NOT_NULL(units); SY_NOT_NULL(colours); SY_NOT_NULL(sample_ids);
+    SY_ALIGNED8(offsets);
+    XP_CHECK_ARG(n_tiles >= n_jobs && n_rows >= n_jobs && n_col_blocks >= n_jobs, "%s: n_tiles, n_rows and n_col_blocks count at least one "
+                 "workgroup per job (got %d, %d, %d for %d jobs)", fn, n_tiles, n_rows, n_col_blocks, n_jobs);
+    const hipStream_t s = (hipStream_t)stream;
+    // algorithmic bytes: the texture, the row pass and the blurred boxes are each written once and read once
+    XpProfScope prof("synth_texture", s, 0.0, 8.0 * (double)arena_floats);
+    hipLaunchKernelGGL(synth_texture_kernel, dim3(n_tiles), dim3(256), 0, s, arena, arena_floats, jobs, offsets, units, n_jobs, colours, n_records,
+                       (uint64_t)seed, sample_ids, nb_blobs, min_contrast, B, H, W);
+    hipLaunchKernelGGL(synth_texture_rows_kernel, dim3(n_rows), dim3(256), 0, s, arena, arena_floats, jobs, offsets, units + (n_jobs + 1), n_jobs,
+                       B, n_records, H, W);
+    hipLaunchKernelGGL(synth_texture_cols_kernel, dim3(n_col_blocks), dim3(256), 0, s, arena, arena_floats, jobs, offsets, units + 2 * (n_jobs + 1),
+                       n_jobs, B, n_records, H, W);
+    XP_LAUNCH_CHECK();
+    return XP_OK;
+}
+
+extern "C" int xp_synth_rasterise_textured(float* frame, const int* records, const float* colours, unsigned long long seed, const int* sample_ids,
+                                           const float* arena, const long long* tex_offsets, int n_records, int B, int H, int W, void* stream) {
+    const char* fn = "xp_synth_rasterise_textured";
+    if (int rc = sy_check_frame(fn, B, H, W)) return rc;
+    XP_CHECK_ARG(n_records >= 1 && n_records <= SY_MAX_REC, "%s: n_records must be in [1, %d] (got %d)", fn, SY_MAX_REC, n_records);
+    SY_NOT_NULL(frame); SY_NOT_NULL(records); SY_NOT_NULL(colours); SY_NOT_NULL(sample_ids); SY_NOT_NULL(arena); SY_NOT_NULL(tex_offsets);
+    SY_ALIGNED8(records); SY_ALIGNED8(tex_offsets);
+    XpProfScope prof("synth_rasterise_textured", (hipStream_t)stream, 0.0, 12.0 * B * H * W);
+    hipLaunchKernelGGL(synth_raster_kernel<true>, xp_tile_grid(W, H, B), dim3(256), 0, (hipStream_t)stream, frame, records, colours, (uint64_t)seed,
+                       sample_ids, arena, tex_offsets, n_records, H, W);
     XP_LAUNCH_CHECK();
     return XP_OK;
 }

@@ -28,8 +28,13 @@ Stated differences from the reference:
   * the checkerboard keeps its neighbours' colours in f64 (the reference rounds them to float16 before comparing);
   * warped grid points are clamped to +-16383 (the rasteriser's 64-bit tests are exact inside that range);
   * images are f32 from the first pixel (the reference carries float64 until the end);
-  * `draw_multiple_polygons` (textured polygons) is NOT implemented: asking for it raises NotImplementedError, and 'all' means the other
-    eight primitives.
+  * `draw_multiple_polygons` (textured polygons) is opt-in: without the dataset key `textured_polygons: true` asking for it raises
+    NotImplementedError and 'all' means the other eight primitives; with the key, 'all' means the nine.  Its polygons are filled with a
+    procedural texture, 3 000 random discs under a box blur, that is never stored as a list: the device draws the discs from the Philox
+    generator (slot KEY_TEXTURE) and blurs each texture only where its polygon needs it (`render`, `_multiple_polygons`);
+  * the reference takes draw_multiple_polygons' background colour as int(np.mean(img)), which is 0 for an image in [0, 1): every colour of a
+    texture is get_random_color(0, min_contrast), raw shifted by 0.5 where raw < min_contrast, whatever the image holds.  Kept: no texture
+    colour depends on the device's mean.  The primitive reads its own min_contrast (0.13), not generation.min_contrast, as there.
 
 Gaussian sizes: the reference reads config['processing'] only, while its shipped YAML writes `preprocessing`, which is therefore silently
 ignored there.  Here both are accepted: a `processing` key given by the caller wins, then `preprocessing`, then the defaults (21, 51)."""
@@ -46,17 +51,18 @@ from . import _lib
 from . import homographies as _hom
 from .utils import dict_update
 
-NOP, CIRCLE, SEGMENT, POLYGON, ELLIPSE, NOISE = range(6)          # XP_SYNTH_* record kinds
+NOP, CIRCLE, SEGMENT, POLYGON, ELLIPSE, NOISE, TEXTURED = range(7)          # XP_SYNTH_* record kinds
 RULE_ABS, RULE_CONTRAST, RULE_DIFFERENT, RULE_REL = range(4)      # XP_SYNTH_RULE_*
 RECORD_INTS, MAX_RECORDS, CANDIDATES, COORD_MAX = 24, 128, 21, 16383
-KEY_BACKGROUND, KEY_NOISE = 6, 7                                  # Philox primitive slots (the photometric primitives hold 0..5)
+KEY_BACKGROUND, KEY_NOISE, KEY_TEXTURE = 6, 7, 8                  # Philox primitive slots (the photometric primitives hold 0..5)
+MAX_TEXTURE_BLOBS, MAX_KSIZE, JOB_INTS = 4096, 500, 16            # XP_SYNTH_MAX_TEXTURE_BLOBS, _MAX_KSIZE, _JOB_INTS
 
 ALL_PRIMITIVES = ['draw_lines', 'draw_polygon', 'draw_multiple_polygons', 'draw_ellipses', 'draw_star', 'draw_checkerboard', 'draw_stripes',
                   'draw_cube', 'gaussian_noise']
 IMPLEMENTED = [p for p in ALL_PRIMITIVES if p != 'draw_multiple_polygons']
 
 DEFAULT_CONFIG = {
-    'length': 1000, 'primitives': 'all', 'on-the-fly': True, 'hdf5-file': None,
+    'length': 1000, 'primitives': 'all', 'textured_polygons': False, 'on-the-fly': True, 'hdf5-file': None,
     'generation_size': [960, 1280], 'image_size': [240, 320], 'keypoints_as_map': True,
     'generation': {
         'min_contrast': 0.1,
@@ -80,14 +86,15 @@ def merge_config(config):
     return cfg
 
 
-def parse_primitives(names):
-    """'all' = the eight implemented primitives; a name or a list of names otherwise.  draw_multiple_polygons raises NotImplementedError."""
+def parse_primitives(names, textured_polygons=False):
+    """'all' = the eight primitives of IMPLEMENTED, or the nine of ALL_PRIMITIVES with textured_polygons; a name or a list of names otherwise.
+    Without textured_polygons the name draw_multiple_polygons raises NotImplementedError."""
     if names == 'all':
-        return list(IMPLEMENTED)
+        return list(ALL_PRIMITIVES if textured_polygons else IMPLEMENTED)
     p = list(names) if isinstance(names, (list, tuple)) else [names]
-    if 'draw_multiple_polygons' in p:
+    if 'draw_multiple_polygons' in p and not textured_polygons:
         raise NotImplementedError("SyntheticShapes: the primitive 'draw_multiple_polygons' (textured polygons) is not implemented; "
-                                  "'all' selects the other eight")
+                                  "'all' selects the other eight (the dataset key textured_polygons: true turns it on)")
     if not p or not set(p) <= set(ALL_PRIMITIVES):
         raise ValueError(f"SyntheticShapes: unknown primitives {sorted(set(p) - set(ALL_PRIMITIVES))}")
     return p
@@ -121,7 +128,7 @@ def make_record(kind, geom=(), n=0, rule=None, angle_cos_sin=None):
     """One draw-list record: kind, integer geometry (circle cx cy; segment x1 y1 x2 y2; polygon x0 y0 x1 y1 ...; ellipse cx cy ax ay), n =
     radius / thickness / vertex count, the colour rule, and for an ellipse (cos, sin) of its angle as f64."""
     g = [_clampi(v) for v in geom]
-    if kind == POLYGON and (n != len(g) // 2 or not 1 <= n <= 8):
+    if kind in (POLYGON, TEXTURED) and (n != len(g) // 2 or not 1 <= n <= 8):
         raise ValueError(f"make_record: a polygon holds 1..8 vertices, got n = {n} with {len(g)} coordinates")
     return {'kind': int(kind), 'geom': g, 'n': int(n), 'rule': rule or rule_abs(0.0), 'cs': angle_cos_sin}
 
@@ -133,7 +140,7 @@ def _bbox(rec, H, W):
     elif k == SEGMENT:
         pad = n // 2 + 1
         x0, y0, x1, y1 = min(g[0], g[2]) - pad, min(g[1], g[3]) - pad, max(g[0], g[2]) + pad, max(g[1], g[3]) + pad
-    elif k == POLYGON:
+    elif k in (POLYGON, TEXTURED):
         x0, y0, x1, y1 = min(g[0::2]), min(g[1::2]), max(g[0::2]), max(g[1::2])
     elif k == ELLIPSE:
         r = max(g[2], g[3]) + 1
@@ -146,7 +153,9 @@ def _bbox(rec, H, W):
 def pack_draw_lists(lists, generation_size):
     """The device tables of B draw lists (`sample_draw_lists`, or hand-made dicts with 'records', 'keypoints', 'threshold', 'blobs',
     'blob_raw', 'bg_ksize', 'is_optical', 'index'): numpy arrays in the layouts of include/xpoint_hip.h (xp_synth_*).  An optional
-    tables['min_contrast'] is the background blobs' (default 0.13, generate_background's own)."""
+    tables['min_contrast'] is the background blobs' (default 0.13, generate_background's own).  A TEXTURED record (a polygon record with
+    'ksize', 'ordinal' and, optionally, 'nb_blobs' (3000) and 'min_contrast' (0.13)) puts its blur size and ordinal into words 22 and 23; the
+    textures of one batch share nb_blobs and min_contrast: tables['texture_blobs'], tables['texture_min_contrast']."""
     H, W = int(generation_size[0]), int(generation_size[1])
     B = len(lists)
     R = max(1, max(len(d['records']) for d in lists))
@@ -163,6 +172,7 @@ def pack_draw_lists(lists, generation_size):
          'thresholds': np.zeros(B, np.float32), 'blob_geom': np.zeros((B, max(NB, 1), 4), np.int32), 'blob_raw': np.zeros((B, max(NB, 1))),
          'bg_ksize': np.zeros(B, np.int32), 'is_optical': np.zeros(B, bool), 'ids': np.zeros(B, np.int32), 'n_blobs': NB}
     t['rules'][:, :, 0] = RULE_ABS
+    texture = set()
     for b, d in enumerate(lists):
         off = 0
         for r, rec in enumerate(d['records']):
@@ -174,6 +184,11 @@ def pack_draw_lists(lists, generation_size):
             row[6:6 + len(g)] = g
             if rec['kind'] == ELLIPSE:
                 row[10:14] = np.array(rec['cs'], np.float64).view(np.int32)
+            if rec['kind'] == TEXTURED:
+                if not 1 <= int(rec['ksize']) <= MAX_KSIZE:
+                    raise ValueError(f"pack_draw_lists: a textured polygon's ksize must be in [1, {MAX_KSIZE}], got {rec['ksize']}")
+                row[22:24] = (rec['ksize'], rec['ordinal'])
+                texture.add((int(rec.get('nb_blobs', 3000)), float(rec.get('min_contrast', 0.13))))
             kind, v, m, r0, r1, cands = rec['rule']
             if (r0 >= r) or (r1 >= r):
                 raise ValueError("pack_draw_lists: a colour rule refers to earlier records only")
@@ -192,6 +207,12 @@ def pack_draw_lists(lists, generation_size):
         t['bg_ksize'][b] = d['bg_ksize']
         t['is_optical'][b] = d['is_optical']
         t['ids'][b] = d['index']
+    if len(texture) > 1:
+        raise ValueError(f"pack_draw_lists: the textured polygons of a batch share nb_blobs and min_contrast, got {sorted(texture)}")
+    if texture:
+        t['texture_blobs'], t['texture_min_contrast'] = texture.pop()
+        if not 0 <= t['texture_blobs'] <= MAX_TEXTURE_BLOBS:
+            raise ValueError(f"pack_draw_lists: nb_blobs must be in [0, {MAX_TEXTURE_BLOBS}], got {t['texture_blobs']}")
     return t
 
 
@@ -273,14 +294,16 @@ def _lines(d, H, W, mc, nb_lines=10):
     return recs, np.array(pts, np.int64).reshape(-1, 2)
 
 
-def _polygon_points(d, H, W, max_sides, min_rad_frac, lo_frac):
+def _polygon_points(d, H, W, max_sides, min_rad_frac, lo_frac, centre=None):
+    """corners on a circle (before the filter), its centre and its radius; centre: the draw of a centre coordinate, d.ri unless given"""
+    centre = centre or d.ri
     n = d.ri(3, max_sides)
     min_dim = min(H, W)
     rad = max(d.u() * min_dim / 2, min_dim / min_rad_frac)
-    x, y = d.ri(int(rad), int(W - rad)), d.ri(int(rad), int(H - rad))
+    x, y = centre(int(rad), int(W - rad)), centre(int(rad), int(H - rad))
     sl = np.linspace(0, 2 * math.pi, n + 1)
     ang = [sl[i] + d.u() * (sl[i + 1] - sl[i]) for i in range(n)]
-    return np.array([[int(x + max(d.u(), lo_frac) * rad * math.cos(a)), int(y + max(d.u(), lo_frac) * rad * math.sin(a))] for a in ang], np.int64), (x, y)
+    return np.array([[int(x + max(d.u(), lo_frac) * rad * math.cos(a)), int(y + max(d.u(), lo_frac) * rad * math.sin(a))] for a in ang], np.int64), (x, y, rad)
 
 
 def _polygon(d, H, W, mc, max_sides=8):
@@ -296,6 +319,43 @@ def _polygon(d, H, W, mc, max_sides=8):
     rec = make_record(POLYGON, pts.reshape(-1).tolist(), len(pts), rule_contrast(d.u(), mc))
     rec['attempts'] = attempts                    # kept for inspection (tests); `pack_draw_lists` does not read it
     return [rec], pts
+
+
+def circles_nested(centre, rad, centres, rads):
+    """draw_primitives.overlap: an accepted circle that contains, or lies inside, the circle (centre, rad)"""
+    return any(math.hypot(centre[0] - c[0], centre[1] - c[1]) + min(rad, r) < max(rad, r) for c, r in zip(centres, rads))
+
+
+def _multiple_polygons(d, H, W, mc, max_sides=8, nb_polygons=30, nb_blobs=3000, min_contrast=0.13, kernel_boundaries=(50, 100)):
+    """draw_multiple_polygons: nb_polygons attempts, each accepted polygon one TEXTURED record; the keypoints are all their vertices.  The
+    draws of one attempt, in this order: the corner count, the radius, the centre x, y (upper end excluded), the corners' angles, then per
+    corner its two radial factors; the corner filter draws nothing; an attempt with fewer than 3 corners left, with an edge that intersects
+    an accepted polygon's edge, or whose circle nests with an accepted circle ends there (no redraw); an accepted one then draws its
+    blur size in [kernel_boundaries) and its base colour.  `mc` (generation.min_contrast) is not read: the textures use `min_contrast`."""
+    if max_sides > 8:
+        raise ValueError(f"draw_multiple_polygons: max_sides must be at most 8 (a polygon record holds 8 vertices), got {max_sides}")
+    if not 0 <= int(nb_blobs) <= MAX_TEXTURE_BLOBS:
+        raise ValueError(f"draw_multiple_polygons: nb_blobs must be in [0, {MAX_TEXTURE_BLOBS}], got {nb_blobs}")
+    recs, edges, centres, rads, pts_all = [], [], [], [], []
+    for _ in range(nb_polygons):
+        pts, (x, y, rad) = _polygon_points(d, H, W, max_sides, 10, 0.4, centre=d.nr)
+        if circles_nested((x, y), rad, centres, rads):          # none of the three rejections draws: their order is free, the cheapest first
+            continue
+        pts = filter_corners(pts)
+        n = len(pts)
+        if n < 3:
+            continue
+        new = [(tuple(pts[i]), tuple(pts[(i + 1) % n])) for i in range(n)]
+        if any(segments_intersect(a, b, p, q) for a, b in edges for p, q in new):
+            continue
+        centres.append((x, y)); rads.append(rad)
+        edges += new
+        ksize, raw = d.nr(kernel_boundaries[0], kernel_boundaries[1]), d.u()
+        rec = make_record(TEXTURED, pts.reshape(-1).tolist(), n, rule_abs((raw + 0.5) % 1.0 if raw < min_contrast else raw))
+        rec.update(ksize=ksize, ordinal=len(recs), nb_blobs=int(nb_blobs), min_contrast=float(min_contrast), circle=(x, y, rad))
+        recs.append(rec)
+        pts_all.append(pts)
+    return recs, np.concatenate(pts_all).astype(np.int64) if pts_all else np.zeros((0, 2), np.int64)
 
 
 def ellipses_separated(max_rad, centre, centres, rads):
@@ -445,7 +505,7 @@ def _noise(d, H, W, mc):
     return [make_record(NOISE)], np.zeros((0, 2), np.int64)
 
 
-_SAMPLERS = {'draw_lines': _lines, 'draw_polygon': _polygon, 'draw_ellipses': _ellipses, 'draw_star': _star, 'draw_checkerboard': _checkerboard,
+_SAMPLERS = {'draw_lines': _lines, 'draw_polygon': _polygon, 'draw_multiple_polygons': _multiple_polygons, 'draw_ellipses': _ellipses, 'draw_star': _star, 'draw_checkerboard': _checkerboard,
              'draw_stripes': _stripes, 'draw_cube': _cube, 'gaussian_noise': _noise}
 
 
@@ -466,7 +526,7 @@ def sample_draw_lists(config, indices, seed, is_optical=None):
     'points' (n, 2) generation-frame (x, y), 'keypoints' (n, 2) image-frame (y, x)}].  config: a merged config (`merge_config`) or the
     caller's partial one.  is_optical: None draws the flag per sample, a bool forces it for every sample."""
     cfg = merge_config(config)
-    prims = parse_primitives(cfg['primitives'])
+    prims = parse_primitives(cfg['primitives'], bool(cfg.get('textured_polygons', False)))
     H, W = (int(v) for v in cfg['generation_size'])
     gen = cfg['generation']
     mc = float(gen.get('min_contrast', 0.1))
@@ -495,12 +555,69 @@ def _gauss_tables(sizes):
     return wts, np.asarray(sizes, np.int32)
 
 
+def _reach(lo, hi, k, n):
+    """(first, last) frame position that the box-blur windows (size k, anchor k // 2) of the positions lo .. hi reach after BORDER_REFLECT_101"""
+    p = np.arange(lo - k // 2, hi - k // 2 + k)
+    if n > 1:
+        p = np.mod(p, 2 * (n - 1))
+        p = np.where(p < n, p, 2 * (n - 1) - p)
+    else:
+        p = np.zeros_like(p)
+    return int(p.min()), int(p.max())
+
+
+def texture_jobs(tables, generation_size):
+    """The work items of the TEXTURED records of packed draw lists, or None when there is none: {'jobs' (J, JOB_INTS) int32, 'offsets' (J, 3)
+    int64, 'units' (3, J + 1) int32, 'tex_offsets' (B, R) int64, 'arena_floats', 'ksize' (min, max)} in the layouts of xp_synth_texture.  A job
+    keeps, in floats of one arena: its texture over the texture box (th x tw: the record's box dilated by the blur window, the reflection at
+    the frame's border folded back), the row pass (th x bw) and the blurred box (bh x bw).  The host knows every box, so the arena is sized
+    exactly: the sum of those three products over the jobs, each at most H W (and far less for the sampler's lists, whose boxes lie in
+    circles that do not nest); never a frame per polygon slot."""
+    H, W = int(generation_size[0]), int(generation_size[1])
+    rec = tables['records']
+    B, R = rec.shape[:2]
+    jobs, offs, units = [], [], [[0], [0], [0]]
+    tex_offsets = np.full((B, R), -1, np.int64)
+    arena = 0
+    for b, r in zip(*np.nonzero(rec[:, :, 0] == TEXTURED)):
+        row = rec[b, r]
+        x0, y0, x1, y1, k, j = (int(v) for v in (*row[1:5], row[22], row[23]))
+        if not 1 <= k <= MAX_KSIZE:
+            raise ValueError(f"SyntheticShapes: a textured polygon's ksize must be in [1, {MAX_KSIZE}], got {k}")
+        if not 0 <= j < MAX_RECORDS:
+            raise ValueError(f"SyntheticShapes: a textured polygon's ordinal must be in [0, {MAX_RECORDS}), got {j}")
+        if x0 > x1 or y0 > y1:
+            continue                                      # the polygon lies outside the frame: it covers no pixel
+        (tx0, tx1), (ty0, ty1) = _reach(x0, x1, k, W), _reach(y0, y1, k, H)
+        bw, bh, tw, th = x1 - x0 + 1, y1 - y0 + 1, tx1 - tx0 + 1, ty1 - ty0 + 1
+        jobs.append([b, r, j, k, x0, y0, x1, y1, tx0, ty0, tx1, ty1] + [0] * (JOB_INTS - 12))
+        offs.append([arena, arena + tw * th, arena + tw * th + bw * th])
+        tex_offsets[b, r] = offs[-1][2]
+        arena += tw * th + bw * th + bw * bh
+        for u, n in zip(units, (-(-tw // 32) * -(-th // 32), th, -(-bw // 64) * -(-bh // 256))):
+            u.append(u[-1] + n)
+    if not jobs:
+        return None
+    if max(u[-1] for u in units) >= 1 << 31:
+        raise ValueError("SyntheticShapes: the textured polygons of one batch need more than 2^31 workgroups; render fewer images at a time")
+    ks = [q[3] for q in jobs]
+    return {'jobs': np.array(jobs, np.int32), 'offsets': np.array(offs, np.int64), 'units': np.array(units, np.int32), 'tex_offsets': tex_offsets,
+            'arena_floats': arena, 'ksize': (min(ks), max(ks))}
+
+
 def render(tables, generation_size, image_size, seed, device, blur_size=21, additional_ir_blur=True, additional_ir_blur_size=51, debug=False):
     """Execute packed draw lists (`pack_draw_lists`) on the device.  Returns (images (B, 1, h, w) f32, keypoint maps (B, h, w) bool), and with
     debug=True a third value: {'background', 'frame' (before the Gaussian), 'blurred' (before the resize), 'bg_mean', 'field_mean', 'colours'}.
     13 kernel launches for any B (11 with additional_ir_blur off or without a thermal sample in the batch, one fewer when the two sizes are
     equal) and one memset.  All tables are uploaded before the first launch and nothing is read back: the host never waits for the batch's own
-    kernels."""
+    kernels.
+
+    A batch that holds a TEXTURED record (draw_multiple_polygons) launches 3 kernels more, whatever B and the number of polygons: the textures,
+    the row and the column pass of their box blur (xp_synth_texture, over the jobs of `texture_jobs`), and the rasteriser is the variant that
+    reads the blurred boxes (xp_synth_rasterise_textured in place of xp_synth_rasterise).  The jobs share one arena of exactly
+    `texture_jobs(...)['arena_floats']` floats (see there).  Any other batch launches what it always did.  debug=True then adds
+    'texture_jobs': per job {'b', 'r', 'j', 'ksize', 'box', 'texture_box' (x0, y0, x1, y1 inclusive), 'texture' (th, tw) unblurred over the
+    texture box, 'blurred' (bh, bw) over the record's box}."""
     import torch
     from ._lib import ptr
     dev = torch.device(device)
@@ -526,6 +643,13 @@ def render(tables, generation_size, image_size, seed, device, blur_size=21, addi
         if additional_ir_blur and not all(bool(o) for o in tables['is_optical']):
             sizes.append([1 if o else additional_ir_blur_size for o in tables['is_optical']])
         gauss = [tuple(up(a) for a in _gauss_tables(sz)) for sz in sizes]
+        tex = texture_jobs(tables, (H, W))
+        if tex:
+            nb, tex_mc = int(tables.get('texture_blobs', 3000)), float(tables.get('texture_min_contrast', 0.13))
+            if not 0 <= nb <= MAX_TEXTURE_BLOBS:
+                raise ValueError(f"SyntheticShapes: nb_blobs must be in [0, {MAX_TEXTURE_BLOBS}], got {nb}")
+            jobs, offsets, units, tex_offsets = up(tex['jobs']), up(tex['offsets']), up(tex['units']), up(tex['tex_offsets'])
+            arena = torch.empty(tex['arena_floats'], dtype=torch.float32, device=dev)
         frame, tmp = torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B, H, W), dtype=torch.float32, device=dev)
         count_ws = torch.empty((B, 128), dtype=torch.int32, device=dev)
         part_ws = torch.empty((B, 128), dtype=torch.float64, device=dev)
@@ -538,9 +662,20 @@ def render(tables, generation_size, image_size, seed, device, blur_size=21, addi
         _lib.call("xp_synth_resolve_colours", ptr(frame), ptr(rules), ptr(vals), ptr(cands), R, cands.shape[1], ptr(part_ws), ptr(colours),
                   ptr(bg_mean), B, H, W, st)
         dbg = {'background': frame.clone(), 'bg_mean': bg_mean, 'field_mean': field_mean, 'colours': colours} if debug else None
-        _lib.call("xp_synth_rasterise", ptr(frame), ptr(recs), ptr(colours), seed, ptr(ids), R, B, H, W, st)
+        if tex:
+            _lib.call("xp_synth_texture", ptr(arena), tex['arena_floats'], ptr(jobs), ptr(offsets), ptr(units), len(tex['jobs']), ptr(colours), R, seed,
+                      ptr(ids), nb, tex_mc, *tex['ksize'], *(int(u[-1]) for u in tex['units']), B, H, W, st)
+            _lib.call("xp_synth_rasterise_textured", ptr(frame), ptr(recs), ptr(colours), seed, ptr(ids), ptr(arena), ptr(tex_offsets), R, B, H, W, st)
+        else:
+            _lib.call("xp_synth_rasterise", ptr(frame), ptr(recs), ptr(colours), seed, ptr(ids), R, B, H, W, st)
         if debug:
             dbg['frame'] = frame.clone()
+            if tex:
+                dbg['texture_jobs'] = []
+                for q, o in zip(tex['jobs'].tolist(), tex['offsets'].tolist()):
+                    bw, bh, tw, th = q[6] - q[4] + 1, q[7] - q[5] + 1, q[10] - q[8] + 1, q[11] - q[9] + 1
+                    dbg['texture_jobs'].append({'b': q[0], 'r': q[1], 'j': q[2], 'ksize': q[3], 'box': tuple(q[4:8]), 'texture_box': tuple(q[8:12]),
+                                                'texture': arena[o[0]:o[0] + tw * th].view(th, tw), 'blurred': arena[o[2]:o[2] + bw * bh].view(bh, bw)})
         for wts, ksz in gauss:
             _lib.call("xp_aug_blur", ptr(frame), ptr(tmp), ptr(wts), ptr(ksz), wts.shape[1], B, H, W, 0, st)
             _lib.call("xp_aug_blur", ptr(tmp), ptr(frame), ptr(wts), ptr(ksz), wts.shape[1], B, H, W, 1, st)
@@ -598,7 +733,7 @@ class SyntheticShapes:
                                       "only on-the-fly generation is implemented")
         if not self.config['keypoints_as_map']:
             raise NotImplementedError("SyntheticShapes: 'keypoints_as_map': false (keypoint lists) is not implemented; the loss takes label maps")
-        self.primitives = parse_primitives(self.config['primitives'])
+        self.primitives = parse_primitives(self.config['primitives'], bool(self.config.get('textured_polygons', False)))
 
     def __len__(self):
         return int(self.config['length'])
