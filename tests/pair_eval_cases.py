@@ -130,10 +130,12 @@ PROJECTIVE = np.array([[1.04, 0.03, -1.7], [-0.02, 0.97, 2.3], [4e-4, -3e-4, 1.0
 PAIR_MAPS = [IDENTITY, TRANSLATION, PROJECTIVE]
 
 # name -> (cap, optical counts, thermal counts, match counts): an image with 0, with 1 and with 300 keypoints (more than one 256-lane tile of
-# queries and of the staged list); match counts 0, 3 (below the 4 a homography needs) and the cap itself
+# queries and of the staged list); match counts 0, 3 (below the 4 a homography needs) and the cap itself; "edges": every image is a query
+# list and a staged list one short of the 256-point tile, exactly on it and one beyond
 KERNEL_CASES = {
     "ragged": (320, [300, 0, 1], [300, 7, 0], [120, 0, 0]),
     "full": (300, [300, 300, 300], [300, 257, 256], [300, 3, 0]),
+    "edges": (257, [255, 256, 257], [257, 255, 256], [255, 4, 0]),
 }
 THRESHOLD_LISTS = {"T1": [3], "T10": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10]}
 

@@ -137,6 +137,57 @@ def test_cli_benchmark_arguments_and_result_keys():
     assert res["homography"]["2"]["h_correctness"]["epsilon_warp_th1"] == 0.25
 
 
+def test_batch_matrices_are_the_shared_helper_and_the_written_expressions():
+    """Both evaluation paths take a sample's 3 x 3 matrices from evaluation._sample_matrices: the rows of pair_eval_matrices equal, bit for bit,
+    what the helper returns for each sample alone, and both equal the expressions the per-sample functions used to write out — h.float().inverse(),
+    torch.mm(h_t, h_o.inverse()) and its .inverse().  Pairs: one given as float64, one with a perspective row, one identity."""
+    from xpoint_amd import evaluation as ev
+    H_o = [torch.tensor([[1.03, 0.02, -3.5], [-0.04, 0.98, 2.25], [0.0, 0.0, 1.0]], dtype=torch.float64),
+           torch.tensor([[0.97, -0.05, 4.0], [0.03, 1.02, -1.5], [3e-4, -2e-4, 1.0]]), torch.eye(3)]
+    H_t = [torch.tensor([[0.99, -0.03, 1.75], [0.05, 1.01, -2.0], [0.0, 0.0, 1.0]], dtype=torch.float64),
+           torch.tensor([[1.01, 0.04, -2.5], [-0.02, 0.96, 3.0], [-1e-4, 5e-4, 1.0]]), torch.eye(3)]
+    B = len(H_o)
+    m1, m2, d1, gt = ev.pair_eval_matrices(torch.stack([h.double() for h in H_o]), torch.stack([h.double() for h in H_t]))
+    assert all(a.dtype == np.float64 for a in (m1, m2, d1, gt)) and m1.shape == m2.shape == d1.shape == (2 * B, 9) and gt.shape == (B, 9)
+    as_row = lambda t: t.numpy().astype(np.float64).reshape(9)
+    for b in range(B):
+        m = ev._sample_matrices(H_o[b][None], H_t[b])                              # any dtype, (3, 3) or (1, 3, 3)
+        assert all(a.dtype == np.float32 and a.shape == (3, 3) for a in m)
+        h_o, h_t = H_o[b].float(), H_t[b].float()
+        gt_b = torch.mm(h_t, h_o.inverse())
+        written = dict(h_o=h_o, h_t=h_t, h_o_inv=h_o.inverse(), h_t_inv=h_t.inverse(), gt=gt_b, gt_inv=gt_b.inverse())
+        for name, t in written.items():
+            assert np.array_equal(getattr(m, name), t.numpy()), (b, name)
+        for name, rows in (("h_o_inv", m1[b]), ("h_t_inv", m1[B + b]), ("h_t", m2[b]), ("h_o", m2[B + b]), ("gt", d1[b]), ("gt_inv", d1[B + b]),
+                           ("gt", gt[b])):
+            assert np.array_equal(rows, as_row(written[name])), (b, name)
+    assert np.array_equal(gt[2], np.eye(3).reshape(9)) and not np.array_equal(gt[1], d1[B + 1])
+
+
+# (true-positive flags in rank order, n_gt) -> {division rule: (precision, recall)}: the arrays compute_desc_dict (div0) and
+# compute_detector_metrics (_div0_one) built inline before they shared _pr_envelope.  The rules differ where tp_cum / n_gt is 0 / 0.
+ENVELOPE_CASES = {
+    "empty": ([], 3, {"div0": ([0.0, 0.0], [0.0, 1.0]), "_div0_one": ([0.0, 0.0], [0.0, 1.0])}),
+    "n_gt = 0": ([False, True, False], 0, {"div0": ([0.5, 0.5, 0.5, 1 / 3, 0.0], [0.0, 0.0, 0.0, 0.0, 1.0]),
+                                           "_div0_one": ([0.5, 0.5, 0.5, 1 / 3, 0.0], [0.0, 1.0, 0.0, 0.0, 1.0])}),
+    "all false positives": ([False, False, False], 2, {"div0": ([0.0] * 5, [0.0, 0.0, 0.0, 0.0, 1.0]),
+                                                       "_div0_one": ([0.0] * 5, [0.0, 0.0, 0.0, 0.0, 1.0])}),
+    "mixed": ([True, False, True, True, False], 4, {"div0": ([1.0, 1.0, 0.75, 0.75, 0.75, 0.6, 0.0], [0.0, 0.25, 0.25, 0.5, 0.75, 0.75, 1.0]),
+                                                    "_div0_one": ([1.0, 1.0, 0.75, 0.75, 0.75, 0.6, 0.0], [0.0, 0.25, 0.25, 0.5, 0.75, 0.75, 1.0])}),
+}
+
+
+@pytest.mark.parametrize("rule", ["div0", "_div0_one"])
+@pytest.mark.parametrize("name", sorted(ENVELOPE_CASES))
+def test_precision_recall_envelope(name, rule):
+    from xpoint_amd import evaluation as ev
+    tp, n_gt, expected = ENVELOPE_CASES[name]
+    for flags in (np.array(tp, bool), np.array(tp)):                 # np.array([]) is float64: what compute_desc_dict sees for an empty match list
+        precision, recall = ev._pr_envelope(flags, n_gt, getattr(ev, rule))
+        assert precision.dtype == recall.dtype == np.float64
+        assert precision.tolist() == expected[rule][0] and recall.tolist() == expected[rule][1]
+
+
 def test_batch_assembly_quirks():
     """repeatability_from_batch / descriptor_from_batch on a hand-made downloaded batch: reference_quirks keeps the last sample's repeatability and
     n_gt, without it every sample counts."""

@@ -25,11 +25,18 @@ def test_points_min_dist_kernel(gpu_lib):
     rng = np.random.default_rng(5)
     a = rng.uniform(-5, 130, (777, 2)); b = rng.integers(0, 128, (1301, 2)).astype(np.float32)
     got = ev._min_dist(a, torch.from_numpy(b).cuda())
-    diff = (a[:, None, :] - b[None].astype(np.float64)).astype(np.float32)
-    ref = np.sqrt(diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]).min(1)
-    assert np.array_equal(got, ref)
+
+    def ref_of(a, b):
+        diff = (a[:, None, :] - b[None].astype(np.float64)).astype(np.float32)
+        return np.sqrt(diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]).min(1)
+    assert np.array_equal(got, ref_of(a, b))
     assert ev._min_dist(a[:3], torch.zeros((0, 2)).cuda()).tolist() == [float("inf")] * 3
     assert ev._min_dist(a[:0], torch.from_numpy(b).cuda()).shape == (0,)
+    # the tile edges: staged lists around the 512-point tile, query counts around the 256-lane block
+    b_dev = torch.from_numpy(b).cuda()
+    for nb in (1, 511, 512, 513):
+        for na in (1, 255, 256, 257):
+            assert np.array_equal(ev._min_dist(a[:na], b_dev[:nb]), ref_of(a[:na], b[:nb])), (na, nb)
 
 
 @pytest.mark.parametrize("seed", [0, 1])

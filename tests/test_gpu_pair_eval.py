@@ -235,27 +235,65 @@ class _FixedNet:
                 {"prob": self.t["prob_thermal"].clone(), "desc": self.t["desc_thermal"]}, None)
 
 
+class _EvalCaseNet(_FixedNet):
+    """make_eval_case(0), then (1), in turn: the outputs for the batches of _eval_case_loader."""
+
+    def __init__(self):
+        self.i = 0
+        self.cases = [_case(s) for s in (0, 1)]
+
+    def __call__(self, data):
+        self.t = self.cases[self.i % 2][1]
+        self.i += 1
+        return super().__call__(data)
+
+
+def _eval_case_loader():
+    for s in (0, 1):
+        c = synth.make_eval_case(s)
+        yield {spec: {"image": torch.zeros(c[f"prob_{spec}"].shape), "valid_mask": torch.from_numpy(c[f"mask_{spec}"]),
+                      "homography": torch.from_numpy(c[f"H_{spec}"])} for spec in ("optical", "thermal")}
+
+
+def test_compute_metrics_is_the_three_per_sample_functions_with_one_match_per_sample(gpu_lib, per_sample, monkeypatch):
+    """compute_metrics over the two eval-case batches (no NMS) against dictionaries assembled by hand from separate calls of
+    compute_repeatability_for_sample, compute_descriptor_for_sample and compute_pts_dist_for_sample (the `per_sample` fixture): equal, the
+    homography part included (the per-sample path estimates every sample as pair 0, so every entry is the same draw).  During the call the
+    matcher is entered once per sample: the descriptor metrics and the corner error share one sampling and one match."""
+    from xpoint_amd import evaluation as ev, utils
+    config = {"prediction": dict(CONFIG["prediction"], nms=0, topk=0)}
+    calls = []
+    matcher = utils.match_descriptors
+
+    def counted(*args, **kwargs):
+        calls.append(1)
+        return matcher(*args, **kwargs)
+    monkeypatch.setattr(utils, "match_descriptors", counted)
+    got = ev.compute_metrics(_EvalCaseNet(), _eval_case_loader(), "cuda", config, 0.015, [1, 3, 5], [2, 4], [1, 2, 3], [3])
+    monkeypatch.undo()
+    n_samples = sum(synth.make_eval_case(s)["prob_optical"].shape[0] for s in (0, 1))
+    assert n_samples >= 4 and len(calls) == n_samples
+
+    nko = per_sample[0]["rep"][1] + per_sample[1]["rep"][1]
+    nkt = per_sample[0]["rep"][2] + per_sample[1]["rep"][2]
+    rep = {"repeatability_mean": {th: np.mean(per_sample[0]["rep"][0][th] + per_sample[1]["rep"][0][th]) for th in (1, 3, 5)},
+           "n_kp_optical": np.mean(nko), "n_kp_thermal": np.mean(nkt)}
+    rep["n_kp_avg"] = (rep["n_kp_optical"] + rep["n_kp_thermal"]) / 2.0
+    _same_tree(got["repeatability"], rep, "repeatability")
+    merged = {th: {k: per_sample[0]["desc"][th][k] + per_sample[1]["desc"][th][k] for k in per_sample[0]["desc"][th]} for th in (2, 4)}
+    assert all(isinstance(merged[th][k], int) for th in (2, 4) for k in ("n_gt_optical", "n_gt_thermal"))
+    _same_tree(got["descriptor"], ev.compute_desc_dict(merged), "descriptor")
+    pts = per_sample[0]["pts"][3] + per_sample[1]["pts"][3]
+    assert len(pts) == n_samples
+    _same_tree(got["homography"], ev.compute_homography_dict({3: pts}, [1, 2, 3]), "homography")
+
+
 def test_compute_metrics_batched_equals_compute_metrics_on_the_eval_cases(gpu_lib):
     """Two batches (make_eval_case 0 and 1, non-trivial homographies and masks), no NMS: with reference_quirks the repeatability and descriptor
     dictionaries are compute_metrics' own, and the homography error agrees on the first sample of every batch."""
     from xpoint_amd import evaluation as ev
     config = {"prediction": dict(CONFIG["prediction"], nms=0, topk=0)}
-
-    class Net(_FixedNet):
-        def __init__(self):
-            self.i = 0
-            self.cases = [_case(s) for s in (0, 1)]
-
-        def __call__(self, data):
-            self.t = self.cases[self.i % 2][1]
-            self.i += 1
-            return super().__call__(data)
-
-    def loader():
-        for s in (0, 1):
-            c = synth.make_eval_case(s)
-            yield {spec: {"image": torch.zeros(c[f"prob_{spec}"].shape), "valid_mask": torch.from_numpy(c[f"mask_{spec}"]),
-                          "homography": torch.from_numpy(c[f"H_{spec}"])} for spec in ("optical", "thermal")}
+    Net, loader = _EvalCaseNet, _eval_case_loader
     ref = ev.compute_metrics(Net(), loader(), "cuda", config, 0.015, [1, 3, 5], [2, 4], [1, 2, 3], [3])
     got = ev.compute_metrics_batched(Net(), loader(), "cuda", config, 0.015, [1, 3, 5], [2, 4], [1, 2, 3], [3])
     _same_tree(got["repeatability"], ref["repeatability"], "repeatability")

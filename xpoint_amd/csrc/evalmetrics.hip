@@ -4,9 +4,11 @@
 // reduced with .sum(1).nonzero()): both only need min_j |a_i - b_j|, so the N x M matrix is never materialised.
 //
 // HBM-bound on paper (8-byte points), in practice a tiny compute kernel: one thread per point of `a`, `b` staged through
-// LDS in tiles.  Arithmetic follows the reference: the difference is formed in f64, cast to f32 (dist.float()), then
-// sqrt(dx*dx + dy*dy) in f32; sqrt is monotonic, so the minimum of the norms is the norm at the minimum squared distance.
+// LDS in tiles of 512 float points.  The walk over a staged tile and its arithmetic (the reference's dist.float()) are
+// xp_near_walk (near_walk.h), shared with pair_eval_warp_near_kernel; sqrt is monotonic, so the minimum of the norms is the
+// norm at the minimum squared distance.
 #include "xp_common.h"
+#include "near_walk.h"
 
 namespace {
 
@@ -21,11 +23,7 @@ __global__ __launch_bounds__(256) void points_min_dist_kernel(const double* __re
         __syncthreads();
         for (int t = threadIdx.x; t < 2 * n; t += 256) s_b[t >> 1][t & 1] = b[2 * j0 + t];
         __syncthreads();
-        for (int j = 0; j < n; ++j) {
-            const float d0 = (float)(a0 - (double)s_b[j][0]), d1 = (float)(a1 - (double)s_b[j][1]);
-            const float d2 = d0 * d0 + d1 * d1;
-            best = fminf(best, d2);
-        }
+        best = xp_near_walk(a0, a1, s_b, n, best);
     }
     if (i < na) out[i] = sqrtf(best);
 }

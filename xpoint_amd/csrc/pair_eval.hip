@@ -8,6 +8,7 @@
 // quantity of pair p is what the pair gives alone and two calls agree bit for bit.  The library is built with -ffp-contract=off: the f64
 // expressions below are evaluated as written, which is what the numpy restatement (tests/pair_eval_cases.py) states.
 #include "xp_common.h"
+#include "near_walk.h"
 
 namespace {
 
@@ -33,7 +34,8 @@ __device__ __forceinline__ void pe_warp(const double* __restrict__ h, double y, 
 // numpy's float64 -> int64 astype as a double: toward zero, INT64_MIN for what does not fit (NaN included); "+ 0.0" turns -0.0 into 0.0
 __device__ __forceinline__ double pe_trunc(double v) { return fabs(v) < 9223372036854775808.0 ? trunc(v) + 0.0 : PE_INT64_MIN; }
 
-// grid (ceil(cap / 256), 2*pairs): one lane owns one query keypoint of image blockIdx.y; the other image's list goes through LDS in tiles.
+// grid (ceil(cap / 256), 2*pairs): one lane owns one query keypoint of image blockIdx.y; the other image's list goes through LDS in tiles,
+// walked by xp_near_walk (near_walk.h) — the loop xp_points_min_dist runs, which is why the batched and per-sample paths agree bit for bit.
 __global__ __launch_bounds__(256) void pair_eval_warp_near_kernel(const int* __restrict__ kp, const int* __restrict__ counts, int pairs, int cap,
                                                                   int H, int W, const double* __restrict__ map1, const double* __restrict__ map2,
                                                                   int truncate, double* __restrict__ warped, uint8_t* __restrict__ inframe,
@@ -64,10 +66,7 @@ __global__ __launch_bounds__(256) void pair_eval_warp_near_kernel(const int* __r
                 s_b[threadIdx.x][1] = (double)(float)k[1];
             }
             __syncthreads();
-            for (int j = 0; j < cnt; ++j) {
-                const float d0 = (float)(wy - s_b[j][0]), d1 = (float)(wx - s_b[j][1]);
-                best = fminf(best, d0 * d0 + d1 * d1);
-            }
+            best = xp_near_walk(wy, wx, s_b, cnt, best);
         }
     }
     if (i < cap) {

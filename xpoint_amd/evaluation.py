@@ -31,6 +31,16 @@ the xp_pair_eval_* kernels, one batched homography estimate per RANSAC threshold
 compute_metrics_batched (compute_metrics' signature and return structure; `reference_quirks` chooses between the reference's per-sample
 overwrites and every sample counting).  `cli benchmark` and training.fit's validation metrics run on it.
 
+What each reference function consists of here (every piece below is written once):
+  compute_repeatability_for_sample      _repeatability_samples (keypoints, counts, warped + filtered sets, nearest distances) + the per-threshold dict
+  compute_repeatability_multispectral   _batch_preamble + _repeatability_samples + its own list, print and nan mean
+  compute_descriptor_for_sample         _check_matcher + _descriptor_samples (keypoints, sampled descriptors, mutual matches) + _descriptor_bookkeeping
+  compute_pts_dist_for_sample           _descriptor_samples + _pts_dist_bookkeeping
+  compute_metrics                       _batch_preamble, then per batch ONE _descriptor_samples for both bookkeeping halves; _MetricsAccumulator
+  compute_metrics_batched               _batch_preamble + pair_metrics_batched; the same _MetricsAccumulator
+  compute_desc_dict / compute_detector_metrics   _pr_envelope with div0 / _div0_one
+  every 3 x 3 matrix of a sample        _sample_matrices (the per-sample functions and pair_eval_matrices: equal bits on both paths by construction)
+
 Reference behaviour kept on purpose (the goldens in tests/golden/g13 come from the reference's own code):
   * inside a batch the repeatability dict and the `n_gt_*` counts are OVERWRITTEN per sample, so they hold the last
     sample's value (benchmark_evaluation.py:447-461, 662-663) — which is why the reference's NN-mAP can exceed 1;
@@ -40,6 +50,7 @@ Reference behaviour kept on purpose (the goldens in tests/golden/g13 come from t
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -87,46 +98,87 @@ def _min_dist(a_np, b_dev_f32):
     a = torch.from_numpy(np.ascontiguousarray(a_np, dtype=np.float64)).to(b_dev_f32.device)
     out = torch.empty((na,), dtype=torch.float32, device=b_dev_f32.device)
     b = b_dev_f32.contiguous()
-    _lib.call("xp_points_min_dist", ctypes.c_void_p(a.data_ptr()), na, ctypes.c_void_p(b.data_ptr()) if nb else None, nb,
-              ctypes.c_void_p(out.data_ptr()), _lib.current_stream())
+    _lib.call("xp_points_min_dist", ptr(a), na, ptr(b) if nb else None, nb, ptr(out), _lib.current_stream())
     return out.cpu().numpy()
+
+
+def _as_list(x):
+    return x if type(x) is list else [x]
+
+
+def _check_matcher(config):
+    m = config['prediction']['matching']
+    if m['method'] != 'bfmatcher' or m.get('knn_matches', False) or not m.get('method_kwargs', {}).get('crossCheck', False):
+        raise NotImplementedError("xpoint_amd.evaluation: the device matcher implements bfmatcher + crossCheck (the reference's configured mode)")
+
+
+SampleMatrices = collections.namedtuple("SampleMatrices", "h_o h_t h_o_inv h_t_inv gt gt_inv")
+
+
+def _sample_matrices(h_o, h_t):
+    """The 3 x 3 matrices of ONE sample as float32 numpy, computed on the host as the reference does: the float32 cast, torch .inverse() of
+    the float32 matrices, gt = h_t @ h_o.inverse() (optical -> thermal) and its inverse.  The only place they are computed: a batched or
+    device inverse would have other bits."""
+    h_o, h_t = h_o.reshape(3, 3).float().cpu(), h_t.reshape(3, 3).float().cpu()
+    h_o_inv = h_o.inverse()
+    gt = torch.mm(h_t, h_o_inv)
+    return SampleMatrices(*(m.numpy() for m in (h_o, h_t, h_o_inv, h_t.inverse(), gt, gt.inverse())))
+
+
+def _default_homographies(data):
+    """Identity homographies (host, float32, (B, 3, 3)) where a batch has none, added to `data` as the reference does."""
+    B = data['optical']['image'].shape[0]
+    for spec in ('optical', 'thermal'):
+        if 'homography' not in data[spec]:
+            data[spec]['homography'] = torch.eye(3, dtype=torch.float32).repeat(B, 1, 1)
+
+
+def _forward_pair(net, data):
+    if not net.takes_pair():
+        return net(data['optical']), net(data['thermal'])
+    out_optical, out_thermal, _ = net(data)
+    return out_optical, out_thermal
+
+
+def _batch_preamble(net, data, device):
+    """What every data-set loop does first: (data on the device, host H_optical, host H_thermal, out_optical, out_thermal)."""
+    _default_homographies(data)
+    H_optical, H_thermal = data['optical']['homography'], data['thermal']['homography']
+    data = utils.data_to_device(data, device)
+    return (data, H_optical, H_thermal) + _forward_pair(net, data)
+
+
+def _repeatability_samples(out_optical, out_thermal, data, H_optical, H_thermal, detection_threshold):
+    """Per sample of a batch: (n_kp_optical, n_kp_thermal, N_optical, N_thermal, d1, d2).  Keypoints are nonzero((prob > thr) * valid_mask);
+    each set goes into the other frame through H.inverse() and the other H with the truncating warp_keypoints and is filtered to the image
+    (N_*: what is left); d1 / d2: for every warped thermal / optical point the distance to the nearest optical / thermal keypoint (the
+    reference: all-pairs norm, then np.min(axis=1)), empty when that image has no keypoint."""
+    samples = []
+    for (prob_o, prob_t, mask_o, mask_t, h_o, h_t) in zip(out_optical['prob'].split(1), out_thermal['prob'].split(1),
+                                                          data['optical']['valid_mask'].split(1), data['thermal']['valid_mask'].split(1),
+                                                          H_optical.split(1), H_thermal.split(1)):
+        kp_optical_d = torch.nonzero((prob_o.squeeze() > detection_threshold).float() * mask_o.squeeze().to(prob_o.device))
+        kp_thermal_d = torch.nonzero((prob_t.squeeze() > detection_threshold).float() * mask_t.squeeze().to(prob_t.device))
+        image_shape = tuple(prob_o.squeeze().shape)
+        m = _sample_matrices(h_o, h_t)
+        warped_optical = filter_points(warp_keypoints(warp_keypoints(kp_optical_d.cpu().numpy(), m.h_o_inv), m.h_t), image_shape)
+        warped_thermal = filter_points(warp_keypoints(warp_keypoints(kp_thermal_d.cpu().numpy(), m.h_t_inv), m.h_o), image_shape)
+        none = np.zeros((0,), np.float32)
+        d1 = _min_dist(warped_thermal, kp_optical_d.float()) if kp_optical_d.shape[0] != 0 else none
+        d2 = _min_dist(warped_optical, kp_thermal_d.float()) if kp_thermal_d.shape[0] != 0 else none
+        samples.append((kp_optical_d.shape[0], kp_thermal_d.shape[0], warped_optical.shape[0], warped_thermal.shape[0], d1, d2))
+    return samples
 
 
 def compute_repeatability_for_sample(out_optical, out_thermal, data, H_optical, H_thermal, detection_threshold, distance_thresh):
     """benchmark_evaluation.py:396-467; same returns: ({th: [repeatability]}, n_kp_optical list, n_kp_thermal list)."""
-    n_kp_optical_member, n_kp_thermal_member = [], []
+    samples = _repeatability_samples(out_optical, out_thermal, data, H_optical, H_thermal, detection_threshold)
     repeatability_member_dict = {}
-    ths = distance_thresh if type(distance_thresh) is list else [distance_thresh]
-    for (prob_o, prob_t, mask_o, mask_t, h_o, h_t) in zip(out_optical['prob'].split(1), out_thermal['prob'].split(1),
-                                                          data['optical']['valid_mask'].split(1),
-                                                          data['thermal']['valid_mask'].split(1),
-                                                          H_optical.split(1), H_thermal.split(1)):
-        kp_optical_d = torch.nonzero((prob_o.squeeze() > detection_threshold).float() * mask_o.squeeze().to(prob_o.device))
-        kp_thermal_d = torch.nonzero((prob_t.squeeze() > detection_threshold).float() * mask_t.squeeze().to(prob_t.device))
-        n_kp_optical_member.append(kp_optical_d.shape[0])
-        n_kp_thermal_member.append(kp_thermal_d.shape[0])
-        kp_optical, kp_thermal = kp_optical_d.cpu().numpy(), kp_thermal_d.cpu().numpy()
-        image_shape = tuple(prob_o.squeeze().shape)
-        h_o = h_o.squeeze().double().cpu(); h_t = h_t.squeeze().double().cpu()
-        h_o32, h_t32 = h_o.float(), h_t.float()       # the reference inverts the float32 matrices (torch .inverse())
-        warped_optical = warp_keypoints(kp_optical, h_o32.inverse().numpy())
-        warped_optical = warp_keypoints(warped_optical, h_t32.numpy())
-        warped_optical = filter_points(warped_optical, image_shape)
-        warped_thermal = warp_keypoints(kp_thermal, h_t32.inverse().numpy())
-        warped_thermal = warp_keypoints(warped_thermal, h_o32.numpy())
-        warped_thermal = filter_points(warped_thermal, image_shape)
-        N_thermal, N_optical = warped_thermal.shape[0], warped_optical.shape[0]
-        # min over the other image's keypoints of the pixel distance (reference: all-pairs norm, then np.min(axis=1))
-        d1 = _min_dist(warped_thermal, kp_optical_d.float())
-        d2 = _min_dist(warped_optical, kp_thermal_d.float())
-        for th in ths:
-            repeatability_member = []
-            count1 = int(np.sum(d1 <= th)) if kp_optical.shape[0] != 0 else 0
-            count2 = int(np.sum(d2 <= th)) if kp_thermal.shape[0] != 0 else 0
-            if N_thermal + N_optical > 0:
-                repeatability_member.append((count1 + count2) / (N_thermal + N_optical))
-            repeatability_member_dict[th] = repeatability_member
-    return repeatability_member_dict, n_kp_optical_member, n_kp_thermal_member
+    for (_, _, N_optical, N_thermal, d1, d2) in samples:
+        for th in _as_list(distance_thresh):                 # overwritten per sample, as in the reference
+            count = int(np.sum(d1 <= th)) + int(np.sum(d2 <= th))
+            repeatability_member_dict[th] = [count / (N_thermal + N_optical)] if N_thermal + N_optical > 0 else []
+    return repeatability_member_dict, [s[0] for s in samples], [s[1] for s in samples]
 
 
 def compute_mAP(precision, recall):
@@ -148,35 +200,35 @@ def _mutual_matches(desc_o, desc_t):
     return m_o, m_t
 
 
-def compute_descriptor_for_sample(prob_optical, prob_thermal, desc_optical, desc_thermal, data, config,
-                                  keypoint_detection_threshold, threshold_keypoints):
-    """benchmark_evaluation.py:588-751; same returns ({th: {tp_*, distance_*, m_score_*, matching_kp_numbers, n_gt_*}}).
-    desc_* are the network's dense descriptor maps (B, D, Hc, Wc) on the device."""
-    method = config['prediction']['matching']['method']
-    if method != 'bfmatcher' or config['prediction']['matching'].get('knn_matches', False) or \
-            not config['prediction']['matching'].get('method_kwargs', {}).get('crossCheck', False):
-        raise NotImplementedError("xpoint_amd.evaluation: the device matcher implements bfmatcher + crossCheck (the reference's configured mode)")
-    descriptor_dict = {th: {} for th in threshold_keypoints} if type(threshold_keypoints) is list else {threshold_keypoints: {}}
+def _descriptor_samples(prob_optical, prob_thermal, desc_optical, desc_thermal, data, keypoint_detection_threshold):
+    """Per sample of a batch, what the descriptor metrics and the corner error both start from: the descriptor keypoints nonzero(prob > thr)
+    of the (already masked) heat maps (kp_o, kp_t: device, (y, x)), the descriptors sampled at them, and their mutual matches (m_o, m_t: see
+    _mutual_matches) — one sampling and ONE matcher call per sample — with the sample's matrices, the heat map's shape and the image's."""
     H_o, W_o = data['optical']['image'].shape[2:]
     H_t, W_t = data['thermal']['image'].shape[2:]
-    per_sample = []
+    samples = []
     for (prob_o, prob_t, h_o, h_t, desc_o, desc_t) in zip(prob_optical, prob_thermal, data['optical']['homography'],
                                                           data['thermal']['homography'], desc_optical, desc_thermal):
-        h_o, h_t = h_o.float().cpu(), h_t.float().cpu()
-        gt_homography = torch.mm(h_t, h_o.inverse())
-        pred_optical = torch.nonzero((prob_o.squeeze() > keypoint_detection_threshold).float())
-        pred_thermal = torch.nonzero((prob_t.squeeze() > keypoint_detection_threshold).float())
-        d_o = utils.interpolate_descriptors(pred_optical, desc_o, H_o, W_o)
-        d_t = utils.interpolate_descriptors(pred_thermal, desc_t, H_t, W_t)
-        matches_optical, matches_thermal = _mutual_matches(d_o, d_t)
-        matches_optical = sorted(matches_optical, key=lambda x: x[2])
-        matches_thermal = sorted(matches_thermal, key=lambda x: x[2])
-        warped_optical = warp_keypoints(pred_optical.cpu().float().numpy(), gt_homography.numpy(), float)
-        warped_thermal = warp_keypoints(pred_thermal.cpu().float().numpy(), gt_homography.inverse().numpy(), float)
+        kp_o = torch.nonzero((prob_o.squeeze() > keypoint_detection_threshold).float())
+        kp_t = torch.nonzero((prob_t.squeeze() > keypoint_detection_threshold).float())
+        m_o, m_t = _mutual_matches(utils.interpolate_descriptors(kp_o, desc_o, H_o, W_o), utils.interpolate_descriptors(kp_t, desc_t, H_t, W_t))
+        samples.append(dict(kp_o=kp_o, kp_t=kp_t, m_o=m_o, m_t=m_t, matrices=_sample_matrices(h_o, h_t),
+                            prob_shape=tuple(prob_o.squeeze().shape), image_hw=(H_o, W_o)))
+    return samples
+
+
+def _descriptor_bookkeeping(samples, threshold_keypoints):
+    """compute_descriptor_for_sample's dictionary from the records of _descriptor_samples."""
+    per_sample = []
+    for s in samples:
+        matches_optical = sorted(s["m_o"], key=lambda x: x[2])
+        matches_thermal = sorted(s["m_t"], key=lambda x: x[2])
+        warped_optical = warp_keypoints(s["kp_o"].cpu().float().numpy(), s["matrices"].gt, float)
+        warped_thermal = warp_keypoints(s["kp_t"].cpu().float().numpy(), s["matrices"].gt_inv, float)
         # rows of the reference's correct_* matrices that contain a True <=> the nearest keypoint is within th
-        near_o = _min_dist(warped_optical, pred_thermal.float())
-        near_t = _min_dist(warped_thermal, pred_optical.float())
-        po, pt = pred_optical.cpu().numpy().astype(np.float64), pred_thermal.cpu().numpy().astype(np.float64)
+        near_o = _min_dist(warped_optical, s["kp_t"].float())
+        near_t = _min_dist(warped_thermal, s["kp_o"].float())
+        po, pt = s["kp_o"].cpu().numpy().astype(np.float64), s["kp_t"].cpu().numpy().astype(np.float64)
 
         def pair_dist(w, other, matches):       # |warped[q] - other[t]| for the matched pairs, in the reference's f32 arithmetic
             if not matches:
@@ -184,12 +236,12 @@ def compute_descriptor_for_sample(prob_optical, prob_thermal, desc_optical, desc
             qi = np.array([m[0] for m in matches]); ti = np.array([m[1] for m in matches])
             diff = (w[qi].astype(np.float64) - other[ti]).astype(np.float32)
             return np.sqrt(diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1])
-        image_shape = tuple(prob_o.squeeze().shape)
         per_sample.append(dict(mo=matches_optical, mt=matches_thermal, near_o=near_o, near_t=near_t,
                                pd_o=pair_dist(warped_optical, pt, matches_optical), pd_t=pair_dist(warped_thermal, po, matches_thermal),
-                               N_optical=filter_points(warped_optical, image_shape).shape[0],
-                               N_thermal=filter_points(warped_thermal, image_shape).shape[0]))
-    for th in descriptor_dict.keys():
+                               N_optical=filter_points(warped_optical, s["prob_shape"]).shape[0],
+                               N_thermal=filter_points(warped_thermal, s["prob_shape"]).shape[0]))
+    descriptor_dict = {}
+    for th in _as_list(threshold_keypoints):
         tp_o, tp_t, dist_o, dist_t, ms_o, ms_t, mk = [], [], [], [], [], [], []
         n_gt_o = n_gt_t = 0
         for s in per_sample:
@@ -208,6 +260,61 @@ def compute_descriptor_for_sample(prob_optical, prob_thermal, desc_optical, desc
     return descriptor_dict
 
 
+def compute_descriptor_for_sample(prob_optical, prob_thermal, desc_optical, desc_thermal, data, config,
+                                  keypoint_detection_threshold, threshold_keypoints):
+    """benchmark_evaluation.py:588-751; same returns ({th: {tp_*, distance_*, m_score_*, matching_kp_numbers, n_gt_*}}).
+    desc_* are the network's dense descriptor maps (B, D, Hc, Wc) on the device."""
+    _check_matcher(config)
+    return _descriptor_bookkeeping(_descriptor_samples(prob_optical, prob_thermal, desc_optical, desc_thermal, data, keypoint_detection_threshold),
+                                   threshold_keypoints)
+
+
+def _pts_dist_bookkeeping(samples, ransac_reporjection_thresholds):
+    """compute_pts_dist_for_sample's dictionary from the records of _descriptor_samples."""
+    pts = []
+    for s in samples:
+        if s["m_o"]:
+            dev = s["kp_o"].device
+            qi = torch.tensor([m[0] for m in s["m_o"]], device=dev); ti = torch.tensor([m[1] for m in s["m_o"]], device=dev)
+            pts.append((s["kp_o"][qi].flip(-1).float(), s["kp_t"][ti].flip(-1).float()))       # cv2.KeyPoint(x = col, y = row)
+        else:
+            pts.append((torch.zeros((0, 2), device=s["kp_o"].device),) * 2)
+    out = {}
+    for th in _as_list(ransac_reporjection_thresholds):
+        member = []
+        for s, (optical_pts, thermal_pts) in zip(samples, pts):
+            H_est, _ = utils.find_homography(optical_pts, thermal_pts, th) if optical_pts.shape[0] >= 4 else (None, None)
+            if H_est is not None:
+                H_o = s["image_hw"][0]
+                corners = np.array([[0, 0], [H_o, 0], [0, s["image_hw"][1]], [H_o, H_o]])
+                gt = warp_keypoints(corners, s["matrices"].gt, float)
+                est = warp_keypoints(corners, H_est, float)
+                member.append(np.linalg.norm(est - gt, axis=1).sum() / 4)
+            else:
+                member.append(999.0)
+        out[th] = member
+    return out
+
+
+def compute_pts_dist_for_sample(prob_optical, prob_thermal, desc_optical, desc_thermal, data, config, keypoint_detection_threshold,
+                                ransac_reporjection_thresholds):
+    """benchmark_evaluation.py:755-830: mean distance of the four image "corners" (the reference's own point list,
+    [[0,0],[H,0],[0,W],[H,H]]) warped by the ground-truth and by the estimated optical->thermal homography; 999.0 when
+    no model could be estimated.  Returns {threshold: [distance per sample]}."""
+    return _pts_dist_bookkeeping(_descriptor_samples(prob_optical, prob_thermal, desc_optical, desc_thermal, data, keypoint_detection_threshold),
+                                 ransac_reporjection_thresholds)
+
+
+def _pr_envelope(tp, n_gt, div):
+    """(precision, recall) of true-positive flags sorted by rank: cumulative sums, recall = tp_cum / n_gt and precision = tp_cum / (tp_cum +
+    fp_cum) under the division rule `div` (div0 or _div0_one: what a zero denominator gives), padded with [0] .. [1] and [0] .. [0], and the
+    precision replaced by its envelope (the maximum over everything to the right)."""
+    tp_cum, fp_cum = np.cumsum(tp), np.cumsum(np.logical_not(tp))
+    recall = np.concatenate([[0], div(tp_cum, n_gt), [1]])
+    precision = np.concatenate([[0], div(tp_cum, tp_cum + fp_cum), [0]])
+    return np.maximum.accumulate(precision[::-1])[::-1], recall
+
+
 def compute_desc_dict(descriptor_metrics_dict):
     """benchmark_evaluation.py:476-558 (host numpy on the per-match lists)."""
     results = {}
@@ -218,12 +325,7 @@ def compute_desc_dict(descriptor_metrics_dict):
             tp = np.array(d[f'tp_{spec}']); dist = np.array(d[f'distance_{spec}'])
             idx = np.argsort(dist)
             tp = tp[idx]; fp = np.logical_not(tp); dist = dist[idx]
-            tp_cum, fp_cum = np.cumsum(tp), np.cumsum(fp)
-            recall = div0(tp_cum, d[f'n_gt_{spec}'])
-            precision = div0(tp_cum, tp_cum + fp_cum)
-            recall = np.concatenate([[0], recall, [1]])
-            precision = np.concatenate([[0], precision, [0]])
-            precision = np.maximum.accumulate(precision[::-1])[::-1]
+            precision, recall = _pr_envelope(tp, d[f'n_gt_{spec}'], div0)
             maps[spec] = compute_mAP(precision, recall)
             out.update({f'tp_{spec}': tp, f'fp_{spec}': fp, f'distance_{spec}': dist, f'recall_{spec}': recall,
                         f'precision_{spec}': precision, f'nn_map_{spec}': maps[spec], f'm_score_{spec}': np.array(d[f'm_score_{spec}'])})
@@ -231,47 +333,6 @@ def compute_desc_dict(descriptor_metrics_dict):
         out['m_score'] = (out['m_score_optical'].mean() + out['m_score_thermal'].mean()) * 0.5
         results[th] = out
     return results
-
-
-def compute_pts_dist_for_sample(prob_optical, prob_thermal, desc_optical, desc_thermal, data, config, keypoint_detection_threshold,
-                                ransac_reporjection_thresholds):
-    """benchmark_evaluation.py:755-830: mean distance of the four image "corners" (the reference's own point list,
-    [[0,0],[H,0],[0,W],[H,H]]) warped by the ground-truth and by the estimated optical->thermal homography; 999.0 when
-    no model could be estimated.  Returns {threshold: [distance per sample]}."""
-    ths = ransac_reporjection_thresholds if type(ransac_reporjection_thresholds) is list else [ransac_reporjection_thresholds]
-    H_o, W_o = data['optical']['image'].shape[2:]
-    H_t, W_t = data['thermal']['image'].shape[2:]
-    samples = []
-    for (prob_o, prob_t, h_o, h_t, desc_o, desc_t) in zip(prob_optical, prob_thermal, data['optical']['homography'],
-                                                          data['thermal']['homography'], desc_optical, desc_thermal):
-        h_o, h_t = h_o.float().cpu(), h_t.float().cpu()
-        gt_homography = torch.mm(h_t, h_o.inverse())
-        pred_optical = torch.nonzero((prob_o.squeeze() > keypoint_detection_threshold).float())
-        pred_thermal = torch.nonzero((prob_t.squeeze() > keypoint_detection_threshold).float())
-        d_o = utils.interpolate_descriptors(pred_optical, desc_o, H_o, W_o)
-        d_t = utils.interpolate_descriptors(pred_thermal, desc_t, H_t, W_t)
-        m_o, _ = _mutual_matches(d_o, d_t)
-        if m_o:
-            qi = torch.tensor([m[0] for m in m_o], device=pred_optical.device); ti = torch.tensor([m[1] for m in m_o], device=pred_optical.device)
-            optical_pts = pred_optical[qi].flip(-1).float()       # cv2.KeyPoint(x = col, y = row)
-            thermal_pts = pred_thermal[ti].flip(-1).float()
-        else:
-            optical_pts = thermal_pts = torch.zeros((0, 2), device=pred_optical.device)
-        samples.append((gt_homography, optical_pts, thermal_pts))
-    out = {}
-    for th in ths:
-        member = []
-        for gt_homography, optical_pts, thermal_pts in samples:
-            H_est, _ = utils.find_homography(optical_pts, thermal_pts, th) if optical_pts.shape[0] >= 4 else (None, None)
-            if H_est is not None:
-                pts = np.array([[0, 0], [H_o, 0], [0, W_o], [H_o, H_o]])
-                gt = warp_keypoints(pts, gt_homography.numpy(), float)
-                est = warp_keypoints(pts, H_est, float)
-                member.append(np.linalg.norm(est - gt, axis=1).sum() / 4)
-            else:
-                member.append(999.0)
-        out[th] = member
-    return out
 
 
 def compute_homography_dict(overall_pts_dist_dict, threshold_warp):
@@ -286,27 +347,47 @@ def compute_homography_dict(overall_pts_dist_dict, threshold_warp):
     return results
 
 
+class _MetricsAccumulator:
+    """The data-set loop's running lists (benchmark_evaluation.py:851-935) and its closing lines (:937-963), for compute_metrics and
+    compute_metrics_batched alike."""
+
+    def __init__(self, thresh_repeatability, thresh_keypoints, ransac_reproj_thresholds):
+        self.repeatability = {th: [] for th in _as_list(thresh_repeatability)}
+        self.n_kp_optical, self.n_kp_thermal = [], []
+        self.descriptor = {th: {} for th in _as_list(thresh_keypoints)}
+        self.pts_dist = {th: [] for th in _as_list(ransac_reproj_thresholds)}
+
+    def add(self, repeatability, descriptor, pts_dist):
+        """One batch: compute_repeatability_for_sample's triple, compute_descriptor_for_sample's dictionary (lists are concatenated, the
+        n_gt_* counts summed) and (RANSAC threshold, [corner error per sample]) pairs."""
+        rep, nko, nkt = repeatability
+        for key, value in rep.items():
+            self.repeatability[key].extend(value)
+        self.n_kp_optical += nko; self.n_kp_thermal += nkt
+        for key, value in descriptor.items():
+            for key2, value2 in value.items():
+                self.descriptor[key][key2] = self.descriptor[key].get(key2, 0 if key2.startswith("n_gt") else []) + value2
+        for key, value in pts_dist:
+            self.pts_dist[key] += value
+
+    def result(self, thresh_warp):
+        out_rep = {'repeatability_mean': {k: np.mean(v) for k, v in self.repeatability.items()},
+                   'n_kp_optical': np.mean(self.n_kp_optical), 'n_kp_thermal': np.mean(self.n_kp_thermal)}
+        out_rep['n_kp_avg'] = (out_rep['n_kp_optical'] + out_rep['n_kp_thermal']) / 2.0
+        return {"repeatability": out_rep, "descriptor": compute_desc_dict(self.descriptor),
+                "homography": compute_homography_dict(self.pts_dist, _as_list(thresh_warp))}
+
+
 def compute_metrics(net, dataloader, device, config, keypoint_detection_threshold=0.015, thresh_repeatability=3, thresh_keypoints=2,
                     thresh_warp=2, ransac_reproj_thresholds=3):
     """benchmark_evaluation.py:832-963.  `dataloader` is any iterable of reference-style `data` dicts; returns
-    {'repeatability': ..., 'descriptor': ..., 'homography': ...} (the last one from this build's estimator)."""
-    repeatability = {th: [] for th in thresh_repeatability} if type(thresh_repeatability) is list else {thresh_repeatability: []}
-    n_kp_optical, n_kp_thermal = [], []
-    descriptor_metrics_dict = {th: {} for th in thresh_keypoints} if type(thresh_keypoints) is list else {thresh_keypoints: {}}
-    rts = ransac_reproj_thresholds if type(ransac_reproj_thresholds) is list else [ransac_reproj_thresholds]
-    overall_pts_dist_dict = {th: [] for th in rts}
+    {'repeatability': ..., 'descriptor': ..., 'homography': ...} (the last one from this build's estimator).  The reference samples and
+    matches every sample twice (once per compute_*_for_sample call); here one _descriptor_samples per batch feeds both."""
+    _check_matcher(config)
+    acc = _MetricsAccumulator(thresh_repeatability, thresh_keypoints, ransac_reproj_thresholds)
     pred = config['prediction']
     for data in dataloader:
-        B = data['optical']['image'].shape[0]
-        for spec in ('optical', 'thermal'):
-            if 'homography' not in data[spec]:
-                data[spec]['homography'] = torch.eye(3, dtype=torch.float32).repeat(B, 1, 1)
-        H_optical, H_thermal = data['optical']['homography'], data['thermal']['homography']
-        data = utils.data_to_device(data, device)
-        if not net.takes_pair():
-            out_optical, out_thermal = net(data['optical']), net(data['thermal'])
-        else:
-            out_optical, out_thermal, _ = net(data)
+        data, H_optical, H_thermal, out_optical, out_thermal = _batch_preamble(net, data, device)
         prob_optical = out_optical['prob'] * data['optical']['valid_mask']
         prob_thermal = out_thermal['prob'] * data['thermal']['valid_mask']
         if pred['nms'] > 0:
@@ -315,29 +396,12 @@ def compute_metrics(net, dataloader, device, config, keypoint_detection_threshol
             prob_optical = utils.box_nms(prob_optical, pred['nms'], keypoint_detection_threshold, **kw)
             out_optical['prob'] = utils.box_nms(out_optical['prob'], pred['nms'], keypoint_detection_threshold, **kw)
             out_thermal['prob'] = utils.box_nms(out_thermal['prob'], pred['nms'], keypoint_detection_threshold, **kw)
-        rep, nko, nkt = compute_repeatability_for_sample(out_optical, out_thermal, data, H_optical, H_thermal,
-                                                         keypoint_detection_threshold, thresh_repeatability)
-        for key, value in rep.items():
-            repeatability[key].extend(value)
-        n_kp_optical += nko; n_kp_thermal += nkt
-        dd = compute_descriptor_for_sample(prob_optical, prob_thermal, out_optical['desc'], out_thermal['desc'], data, config,
-                                           keypoint_detection_threshold, thresh_keypoints)
-        for key, value in dd.items():
-            for key2, value2 in value.items():
-                if key2.startswith("n_gt"):
-                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, 0) + value2
-                else:
-                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, []) + value2
-        pd = compute_pts_dist_for_sample(prob_optical, prob_thermal, out_optical['desc'], out_thermal['desc'], data, config,
-                                         keypoint_detection_threshold, rts)
-        for key, value in pd.items():
-            overall_pts_dist_dict[key] += value
-    out_rep = {'repeatability_mean': {k: np.mean(v) for k, v in repeatability.items()},
-               'n_kp_optical': np.mean(n_kp_optical), 'n_kp_thermal': np.mean(n_kp_thermal)}
-    out_rep['n_kp_avg'] = (out_rep['n_kp_optical'] + out_rep['n_kp_thermal']) / 2.0
-    tw = thresh_warp if type(thresh_warp) is list else [thresh_warp]
-    return {"repeatability": out_rep, "descriptor": compute_desc_dict(descriptor_metrics_dict),
-            "homography": compute_homography_dict(overall_pts_dist_dict, tw)}
+        samples = _descriptor_samples(prob_optical, prob_thermal, out_optical['desc'], out_thermal['desc'], data, keypoint_detection_threshold)
+        acc.add(compute_repeatability_for_sample(out_optical, out_thermal, data, H_optical, H_thermal, keypoint_detection_threshold,
+                                                 thresh_repeatability),
+                _descriptor_bookkeeping(samples, thresh_keypoints),
+                _pts_dist_bookkeeping(samples, _as_list(ransac_reproj_thresholds)).items())
+    return acc.result(thresh_warp)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -346,27 +410,14 @@ def compute_metrics(net, dataloader, device, config, keypoint_detection_threshol
 PAIR_EVAL_MAX_THRESHOLDS = 16          # thresholds per xp_pair_eval_count launch (longer lists take several launches)
 
 
-def _as_list(x):
-    return x if type(x) is list else [x]
-
-
 def pair_eval_matrices(H_o, H_t):
-    """The 3 x 3 matrices of one batch, computed on the HOST one sample at a time exactly as the per-sample functions compute them (float32
-    torch .inverse(), gt = h_t @ h_o.inverse(); a batched or device inverse would have other bits).  H_o, H_t: (B, 3, 3).  Returns float64 numpy
-    arrays: rep_map1, rep_map2, desc_map1 (2B, 9) — per image, optical images first — and gt (B, 9)."""
-    B = int(H_o.shape[0])
-    m1, m2, d1 = [[None] * (2 * B) for _ in range(3)]
-    gts = []
-    for b in range(B):
-        h_o = H_o[b].squeeze().double().cpu().float()
-        h_t = H_t[b].squeeze().double().cpu().float()
-        m1[b], m2[b] = h_o.inverse().numpy(), h_t.numpy()                 # compute_repeatability_for_sample: optical -> scene -> thermal
-        m1[B + b], m2[B + b] = h_t.inverse().numpy(), h_o.numpy()
-        gt = torch.mm(h_t, h_o.inverse())                                 # compute_descriptor_for_sample
-        d1[b], d1[B + b] = gt.numpy(), gt.inverse().numpy()
-        gts.append(gt.numpy())
+    """The 3 x 3 matrices of one batch: _sample_matrices of every sample (the host computation the per-sample functions use), laid out for the
+    kernels.  H_o, H_t: (B, 3, 3).  Returns float64 numpy arrays: rep_map1, rep_map2, desc_map1 (2B, 9) — per image, optical images first —
+    and gt (B, 9)."""
+    ms = [_sample_matrices(h_o, h_t) for h_o, h_t in zip(H_o, H_t)]
     f = lambda rows: np.stack([np.asarray(r, dtype=np.float64).reshape(9) for r in rows])
-    return f(m1), f(m2), f(d1), f(gts)
+    return (f([m.h_o_inv for m in ms] + [m.h_t_inv for m in ms]), f([m.h_t for m in ms] + [m.h_o for m in ms]),      # optical -> scene -> thermal
+            f([m.gt for m in ms] + [m.gt_inv for m in ms]), f([m.gt for m in ms]))
 
 
 def _pe_warp_near(kp, counts, P, cap, H, W, map1, map2, truncate):
@@ -423,8 +474,8 @@ def pair_metrics_batched(prob_rep_o, prob_rep_t, prob_desc_o, prob_desc_t, desc_
     host, one upload per batch).  cap: the capacity of the ragged lists; when it is given (prediction.topk > 0 bounds every list) nothing is
     read back, otherwise the largest count is read once.
 
-    Launch plan: two xp_extract_keypoints (each over the 2B stacked maps), one xp_sample_descriptors, ONE xp_match_mnn over the B pairs (the
-    per-sample functions match every sample twice), xp_pair_eval_warp_near + xp_pair_eval_count for the repeatability set, warp_near +
+    Launch plan: two xp_extract_keypoints (each over the 2B stacked maps), one xp_sample_descriptors, ONE xp_match_mnn over the B pairs (compute_metrics
+    makes one call per sample), xp_pair_eval_warp_near + xp_pair_eval_count for the repeatability set, warp_near +
     match_dist + count for the descriptor set, xp_gather_match_points, and per RANSAC threshold one xp_find_homography and one
     xp_pair_eval_corner_error.  The reference's match order (sorted by distance, equal distances by ascending query index for query = optical
     and by ascending target index for query = thermal) comes from torch's stable sort on the device.
@@ -570,21 +621,11 @@ def compute_metrics_batched(net, dataloader, device, config, keypoint_detection_
     ths_rep, ths_kp = _as_list(thresh_repeatability), _as_list(thresh_keypoints)
     rts = _as_list(ransac_reproj_thresholds)
     pred = config['prediction']
-    m = pred['matching']
-    if m['method'] != 'bfmatcher' or m.get('knn_matches', False) or not m.get('method_kwargs', {}).get('crossCheck', False):
-        raise NotImplementedError("xpoint_amd.evaluation: the device matcher implements bfmatcher + crossCheck (the reference's configured mode)")
+    _check_matcher(config)
     batches = []
     for data in dataloader:
+        data, H_optical, H_thermal, out_optical, out_thermal = _batch_preamble(net, data, device)
         B = data['optical']['image'].shape[0]
-        for spec in ('optical', 'thermal'):
-            if 'homography' not in data[spec]:
-                data[spec]['homography'] = torch.eye(3, dtype=torch.float32).repeat(B, 1, 1)
-        H_optical, H_thermal = data['optical']['homography'], data['thermal']['homography']
-        data = utils.data_to_device(data, device)
-        if not net.takes_pair():
-            out_optical, out_thermal = net(data['optical']), net(data['thermal'])
-        else:
-            out_optical, out_thermal, _ = net(data)
         mask_o, mask_t = data['optical']['valid_mask'], data['thermal']['valid_mask']
         maps = [out_thermal['prob'] * mask_t, out_optical['prob'] * mask_o, out_optical['prob'], out_thermal['prob']]
         cap = None
@@ -596,31 +637,13 @@ def compute_metrics_batched(net, dataloader, device, config, keypoint_detection_
                 cap = int(pred['topk'])
         batches.append(pair_metrics_batched(maps[2], maps[3], maps[1], maps[0], out_optical['desc'], out_thermal['desc'], H_optical, H_thermal,
                                             keypoint_detection_threshold, ths_rep, ths_kp, rts, cap=cap, mask_rep_o=mask_o, mask_rep_t=mask_t))
-    host = download_pair_metrics(batches)
-    repeatability = {th: [] for th in ths_rep}
-    n_kp_optical, n_kp_thermal = [], []
-    descriptor_metrics_dict = {th: {} for th in ths_kp}
-    overall_pts_dist_dict = {th: [] for th in rts}
-    for r in host:
+    acc = _MetricsAccumulator(ths_rep, ths_kp, rts)
+    for r in download_pair_metrics(batches):
         if bool(r["overflow"]):
             raise _lib.XPointHipError("compute_metrics_batched: a keypoint list is longer than its capacity (prediction.topk)")
-        rep, nko, nkt = repeatability_from_batch(r, ths_rep, reference_quirks)
-        for key, value in rep.items():
-            repeatability[key].extend(value)
-        n_kp_optical += nko; n_kp_thermal += nkt
-        for key, value in descriptor_from_batch(r, ths_kp, reference_quirks).items():
-            for key2, value2 in value.items():
-                if key2.startswith("n_gt"):
-                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, 0) + value2
-                else:
-                    descriptor_metrics_dict[key][key2] = descriptor_metrics_dict[key].get(key2, []) + value2
-        for i, th in enumerate(rts):
-            overall_pts_dist_dict[th] += [float(v) for v in r["corner_error"][i]]
-    out_rep = {'repeatability_mean': {k: np.mean(v) for k, v in repeatability.items()},
-               'n_kp_optical': np.mean(n_kp_optical), 'n_kp_thermal': np.mean(n_kp_thermal)}
-    out_rep['n_kp_avg'] = (out_rep['n_kp_optical'] + out_rep['n_kp_thermal']) / 2.0
-    return {"repeatability": out_rep, "descriptor": compute_desc_dict(descriptor_metrics_dict),
-            "homography": compute_homography_dict(overall_pts_dist_dict, _as_list(thresh_warp))}
+        acc.add(repeatability_from_batch(r, ths_rep, reference_quirks), descriptor_from_batch(r, ths_kp, reference_quirks),
+                [(th, [float(v) for v in r["corner_error"][i]]) for i, th in enumerate(rts)])
+    return acc.result(thresh_warp)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -665,7 +688,6 @@ def tp_fp_dist_batched(prob, keypoints, zero_threshold=1e-4, distance_thresh=2.0
     lab = kp.view(torch.uint8) if kp.dtype == torch.bool else (kp if kp.dtype == torch.uint8 else (kp != 0).view(torch.uint8))
     HW = H * W
     dev = p.device
-    v = ctypes.c_void_p
     with torch.cuda.device(dev):
         st = _lib.current_stream(dev)
         cand = torch.empty((B, HW), dtype=torch.float32, device=dev)
@@ -673,11 +695,11 @@ def tp_fp_dist_batched(prob, keypoints, zero_threshold=1e-4, distance_thresh=2.0
         first = torch.empty((B, HW), dtype=torch.int32, device=dev)
         within = torch.empty((B, HW), dtype=torch.int32, device=dev)
         counts = torch.empty((2, B), dtype=torch.int32, device=dev)
-        _lib.call("xp_detector_eval_claim", v(p.data_ptr()), v(lab.data_ptr()), B, H, W, float(zero_threshold), float(distance_thresh),
-                  v(cand.data_ptr()), v(winner.data_ptr()), v(first.data_ptr()), v(within.data_ptr()), v(counts[0].data_ptr()),
-                  v(counts[1].data_ptr()), st)
+        _lib.call("xp_detector_eval_claim", ptr(p), ptr(lab), B, H, W, float(zero_threshold), float(distance_thresh),
+                  ptr(cand), ptr(winner), ptr(first), ptr(within), ptr(counts[0]),
+                  ptr(counts[1]), st)
         tp_pix = torch.empty((B, HW), dtype=torch.uint8, device=dev)
-        _lib.call("xp_detector_eval_resolve", v(cand.data_ptr()), v(winner.data_ptr()), v(first.data_ptr()), B, H, W, v(tp_pix.data_ptr()), st)
+        _lib.call("xp_detector_eval_resolve", ptr(cand), ptr(winner), ptr(first), B, H, W, ptr(tp_pix), st)
         del winner, first
         # the rank order = the order of the u64 keys: descending probability, equal ones by ascending pixel index (the sort is stable and
         # its input is in pixel order); non-candidates are 0 in `cand` and come last.  One image at a time: a 1-D sort's temporaries
@@ -689,15 +711,15 @@ def tp_fp_dist_batched(prob, keypoints, zero_threshold=1e-4, distance_thresh=2.0
         del cand
         tp_s = torch.empty((B, HW), dtype=torch.bool, device=dev)
         cnt_s = torch.empty((B, HW), dtype=torch.int32, device=dev)
-        _lib.call("xp_detector_eval_gather", v(rank_pix.data_ptr()), v(tp_pix.data_ptr()), v(within.data_ptr()), v(counts[0].data_ptr()), B, H, W,
-                  v(tp_s.data_ptr()), v(cnt_s.data_ptr()), st)
+        _lib.call("xp_detector_eval_gather", ptr(rank_pix), ptr(tp_pix), ptr(within), ptr(counts[0]), B, H, W,
+                  ptr(tp_s), ptr(cnt_s), st)
         del tp_pix, within
         incl = torch.cumsum(cnt_s.view(-1), 0, dtype=torch.int64)
         host = torch.cat([counts.view(-1).to(torch.int64), incl.view(B, HW)[:, -1]]).cpu().tolist()         # the one synchronisation
         n_cand, n_gt, ends = host[:B], host[B:2 * B], [0] + host[2 * B:]
         dist = torch.empty((ends[-1],), dtype=torch.float32, device=dev)
-        _lib.call("xp_detector_eval_fill_dist", v(rank_pix.data_ptr()), v(lab.data_ptr()), v(incl.data_ptr()), v(cnt_s.data_ptr()), B, H, W,
-                  float(distance_thresh), v(dist.data_ptr()) if ends[-1] else None, ends[-1], st)
+        _lib.call("xp_detector_eval_fill_dist", ptr(rank_pix), ptr(lab), ptr(incl), ptr(cnt_s), B, H, W,
+                  float(distance_thresh), ptr(dist) if ends[-1] else None, ends[-1], st)
     out = []
     for b in range(B):
         tp = tp_s[b, :n_cand[b]]
@@ -753,16 +775,9 @@ def compute_detector_metrics(net, dataloader, device, config):
     tp = np.concatenate(tp) if tp else np.zeros((0,), bool)
     prob = np.concatenate(prob) if prob else np.zeros((0,), np.float64)
     dist = np.concatenate(dist) if dist else np.zeros((0,), np.float64)
-    fp = np.logical_not(tp)
     sort_idx = np.argsort(-prob, kind="stable")
-    tp, fp, prob = tp[sort_idx], fp[sort_idx], prob[sort_idx]
-    tp_cum, fp_cum = np.cumsum(tp), np.cumsum(fp)
-    recall = _div0_one(tp_cum, n_gt)
-    precision = _div0_one(tp_cum, tp_cum + fp_cum)
-    recall = np.concatenate([[0], recall, [1]])
-    precision = np.concatenate([[0], precision, [0]])
-    precision = np.maximum.accumulate(precision[::-1])[::-1]
-    return precision, recall, prob, dist
+    precision, recall = _pr_envelope(tp[sort_idx], n_gt, _div0_one)
+    return precision, recall, prob[sort_idx], dist
 
 
 def compute_repeatability_multispectral(net, dataloader, device, config, distance_thresh=3, verbose=False):
@@ -776,40 +791,16 @@ def compute_repeatability_multispectral(net, dataloader, device, config, distanc
     pred = config['prediction']
     for data in dataloader:
         detection_threshold = pred['detection_threshold']
-        B = data['optical']['image'].shape[0]
-        H_optical = data['optical']['homography'] if 'homography' in data['optical'] else torch.eye(3, 3).repeat(B, 1, 1)
-        H_thermal = data['thermal']['homography'] if 'homography' in data['thermal'] else torch.eye(3, 3).repeat(B, 1, 1)
-        data = utils.data_to_device(data, device)
-        if not net.takes_pair():
-            out_optical, out_thermal = net(data['optical']), net(data['thermal'])
-        else:
-            out_optical, out_thermal, _ = net(data)
+        data, H_optical, H_thermal, out_optical, out_thermal = _batch_preamble(net, data, device)
         if pred['nms'] > 0:
             kw = dict(keep_top_k=pred['topk'], on_cpu=pred.get('cpu_nms', False))
             out_optical['prob'] = utils.box_nms(out_optical['prob'], pred['nms'], detection_threshold, **kw)
             out_thermal['prob'] = utils.box_nms(out_thermal['prob'], pred['nms'], detection_threshold, **kw)
-        for (prob_o, prob_t, mask_o, mask_t, h_o, h_t) in zip(out_optical['prob'].split(1), out_thermal['prob'].split(1),
-                                                              data['optical']['valid_mask'].split(1), data['thermal']['valid_mask'].split(1),
-                                                              H_optical.split(1), H_thermal.split(1)):
-            kp_optical_d = torch.nonzero((prob_o.squeeze() > detection_threshold).float() * mask_o.squeeze().to(prob_o.device))
-            kp_thermal_d = torch.nonzero((prob_t.squeeze() > detection_threshold).float() * mask_t.squeeze().to(prob_t.device))
-            n_kp_optical.append(kp_optical_d.shape[0])
-            n_kp_thermal.append(kp_thermal_d.shape[0])
-            kp_optical, kp_thermal = kp_optical_d.cpu().numpy(), kp_thermal_d.cpu().numpy()
-            image_shape = tuple(prob_o.squeeze().shape)
-            h_o32, h_t32 = h_o.squeeze().float().cpu(), h_t.squeeze().float().cpu()
-            warped_optical = warp_keypoints(kp_optical, h_o32.inverse().numpy())
-            warped_optical = warp_keypoints(warped_optical, h_t32.numpy())
-            warped_optical = filter_points(warped_optical, image_shape)
-            warped_thermal = warp_keypoints(kp_thermal, h_t32.inverse().numpy())
-            warped_thermal = warp_keypoints(warped_thermal, h_o32.numpy())
-            warped_thermal = filter_points(warped_thermal, image_shape)
-            N_thermal, N_optical = warped_thermal.shape[0], warped_optical.shape[0]
-            count1 = count2 = 0
-            if kp_optical.shape[0] != 0:
-                count1 = int(np.sum(_min_dist(warped_thermal, kp_optical_d.float()) <= distance_thresh))
-            if kp_thermal.shape[0] != 0:
-                count2 = int(np.sum(_min_dist(warped_optical, kp_thermal_d.float()) <= distance_thresh))
+        for (nko, nkt, N_optical, N_thermal, d1, d2) in _repeatability_samples(out_optical, out_thermal, data, H_optical, H_thermal,
+                                                                               detection_threshold):
+            n_kp_optical.append(nko)
+            n_kp_thermal.append(nkt)
+            count1, count2 = int(np.sum(d1 <= distance_thresh)), int(np.sum(d2 <= distance_thresh))
             if N_thermal + N_optical > 0:
                 repeatability.append((count1 + count2) / (N_thermal + N_optical))
                 if verbose:
@@ -859,11 +850,7 @@ def desc_process_and_display_sample(net, dataset, device, config, args):
         data = utils.data_to_device(data, device)
         data = utils.data_unsqueeze(data, 0)
         with _EventSpan() as t_fwd:
-            if not net.takes_pair():
-                out_optical = net(data['optical'])
-                out_thermal = net(data['thermal'])
-            else:
-                out_optical, out_thermal, out_hm = net(data)
+            out_optical, out_thermal = _forward_pair(net, data)
         time_dict_seconds["two_forward"].append(t_fwd.seconds())
         with _EventSpan() as t_nms:
             if pred['nms'] > 0:
@@ -873,9 +860,7 @@ def desc_process_and_display_sample(net, dataset, device, config, args):
                                                     keep_top_k=pred['topk'], on_cpu=pred['cpu_nms'])
         time_dict_seconds["nms"].append(t_nms.seconds())
         n = data['optical']['image'].shape[0]
-        for spec in ('optical', 'thermal'):                 # add homography to data if not available (reference :88-92)
-            if 'homography' not in data[spec].keys():
-                data[spec]['homography'] = torch.eye(3, dtype=torch.float32).to(device).view(1, 3, 3).repeat(n, 1, 1)
+        _default_homographies(data)                         # reference :88-92
         H, W = data['optical']['image'].shape[2:]
         for i in range(n):
             prob_optical, prob_thermal = out_optical['prob'][i], out_thermal['prob'][i]
